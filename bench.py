@@ -6,7 +6,10 @@ index/record.go would (auto-detected format, full validation, offset table left 
 A "step" is one complete build: detect + index kernel + finalize.  N>1: the file is
 N x 10 GiB, one slab per GPU (weak scaling), with one RCCL all-gather of slab summaries.
 
-Prints one JSON line (rank 0).  --check verifies every row against the generator.
+Prints one JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints
+that line.  --full adds everything beside the headline figure: every row checked against the
+generator (--no-check skips it), the streaming floor, the CPU baseline and the PMC traffic
+lookup.  --dump-outputs DIR writes what the last timed build returned as .npy files.
 """
 from __future__ import annotations
 
@@ -42,13 +45,20 @@ def parse():
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"),
                     help="N>1: weak = N x size-gib; strong = one total-gib file cut into N slabs (configs[4])")
     ap.add_argument("--total-gib", type=float, default=80.0, help="--scaling strong: the node file size")
-    ap.add_argument("--cpu-sec", type=float, default=10.0, help="CPU baseline budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the row-by-row parity check, the "
+                         "streaming floor, the CPU baseline and the PMC traffic lookup (off: none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (record count, a fixed sample of "
+                         "the row table) as DIR/<name>.npy (device-resident record / line builds on one GPU)")
+    ap.add_argument("--cpu-sec", type=float, default=10.0, help="--full: CPU baseline budget (0 = skip)")
     ap.add_argument("--cpu-sample-gib", type=float, default=1.0)
-    ap.add_argument("--check", action="store_true", default=True)
+    ap.add_argument("--check", action="store_true", default=True, help="--full: check the rows (the default)")
     ap.add_argument("--no-check", dest="check", action="store_false")
     ap.add_argument("--no-floor", dest="floor", action="store_false", default=True,
-                    help="skip the box's streaming floor (k_stream_floor) printed beside record / line builds")
-    ap.add_argument("--pmc", default=None, help="rocprofv3 PMC summary (default: the newest profiles/r*/pmc_<fmt>.json on these sources)")
+                    help="--full: skip the box's streaming floor (k_stream_floor) printed beside record / line builds")
+    ap.add_argument("--pmc", default=None,
+                    help="--full: rocprofv3 PMC summary (default: the newest profiles/r*/pmc_<fmt>.json on these sources)")
     ap.add_argument("--filter", default="fq2fa", choices=("fq2fa", "anonymize"), help="--kind filter: which filter")
     ap.add_argument("--kind", default="record", choices=("record", "line", "chunkrecord", "filter"),
                     help="line: the line indexer (index/line.go) over the same synthetic file")
@@ -67,9 +77,36 @@ def parse():
     ap.add_argument("--e2e", action="store_true",
                     help="host-memory build (POSTed body): pinned H2D staging + kernel + table D2H")
     a = ap.parse_args()
+    if a.steps < 1 or (a.warmup is not None and a.warmup < 0):
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.warmup is None:
         a.warmup = 100 if (a.kind in ("record", "line") and not a.e2e and not a.subset) else 3
+    if a.dump_outputs and (a.gpus != 1 or a.scaling == "strong" or a.e2e or a.subset or a.kind not in ("record", "line")):
+        ap.error("--dump-outputs covers the device-resident record and line builds on one GPU")
+    if not a.full:  # a plain run: the timed steps and the result line only
+        a.check, a.floor, a.cpu_sec = False, False, 0.0
     return a
+
+
+DUMP_EDGE, DUMP_DRAW, DUMP_SEED = 1 << 18, 1 << 20, 0x5EED
+
+
+def dump_outputs(dirpath: str, rows, count: int):
+    """--dump-outputs: what the last timed build handed its caller -- the record count and the
+    (offset, length) table it left in HBM -- as float64 .npy files (offsets and lengths stay below
+    2^53, so float64 holds them exactly).  The table of a 10 GiB file is ~0.5 GB, so a fixed sample
+    of its rows is written (38 MB): the first and the last 2^18 and a seeded draw of 2^20 between.
+    An offset is the sum of every length before it, so a sampled row also witnesses the rows ahead
+    of it.  rows_sample_ids.npy holds the sampled row numbers."""
+    os.makedirs(dirpath, exist_ok=True)
+    draw = np.random.default_rng(DUMP_SEED).integers(0, max(count, 1), size=DUMP_DRAW)
+    ids = np.unique(np.concatenate([np.arange(min(count, DUMP_EDGE)), draw,
+                                    np.arange(max(count - DUMP_EDGE, 0), count)]))
+    ids = ids[ids < count]
+    tab = rows.rows(count)
+    np.save(os.path.join(dirpath, "count.npy"), np.array([count], dtype=np.float64))
+    np.save(os.path.join(dirpath, "rows_sample_ids.npy"), ids.astype(np.float64))
+    np.save(os.path.join(dirpath, "rows_sample.npy"), tab[ids].astype(np.float64))
 
 
 def cpu_threads(sample: np.ndarray, cuts, fmt: str, budget_s: float, oracle):
@@ -260,12 +297,14 @@ def main():
            if a.fmt == "fastq" else f"fasta record index, {a.size_gib:g} GiB (BASELINE configs[2])",
            "records": count, "bytes": size, "tile": TILE, "parallelism": "single slab",
            "exchange": "none (one slab: no collective)"}
-    traffic = None  # the newest round's summary taken on these kernel sources (--pmc: that file only)
-    for path in ([a.pmc] if a.pmc else sorted(glob.glob(os.path.join(ROOT, "profiles", "r*", f"pmc_{a.fmt}.json")),
-                                                reverse=True)):
+    traffic = None  # --full: the newest round's summary taken on these kernel sources (--pmc: that file only)
+    pmcs = [a.pmc] if a.pmc else sorted(glob.glob(os.path.join(ROOT, "profiles", "r*", f"pmc_{a.fmt}.json")), reverse=True)
+    for path in (pmcs if a.full else []):
         traffic = load_pmc(path, {"fmt": a.fmt, "bytes": size}, kernel)
         if traffic is not None:
             break
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rows, count)
     out = {
         "metric": METRIC,
         "value": round(size / (ms * 1e-3) / GIB, 2),
@@ -339,6 +378,8 @@ def line_bench(a, ctx, sf, data, size):
     # k_line_tiles writes 2-B '\n' positions and 16 B per tile; k_index1 the final 16-B rows
     kernel = "k_line_tiles" if tiles else "k_index1"
     alg = size + 2 * r.count + 16 * ntiles if tiles else size + 16 * r.count
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rows, r.count)
     # parity (size-independent properties): rows tile the file, every row but the last ends in '\n'
     tab = rows.rows(r.count)
     ok = r.ok and int(tab[0, 0]) == 0 and bool(np.all(tab[1:, 0] == tab[:-1, 0] + tab[:-1, 1])) and \

@@ -15,7 +15,7 @@ if [ "$CALL" = b ]; then
   tail -2 $O/pytest_gpu.log
   grep -E "GiB/s end to end" $O/pytest_gpu.log
   step driver-bench
-  timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err || { tail -20 $O/bench_driver_cmd.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err || { tail -20 $O/bench_driver_cmd.err; exit 1; }
   cat $O/bench_driver_cmd.json
   step copies
   timeout -k 10 300 python -u tools/probes/copy_pmc.py --copies 4 --per 4 > $O/copies.json 2> $O/copies.err || { tail -20 $O/copies.err; exit 1; }
@@ -28,7 +28,7 @@ if [ "$CALL" = c ]; then  # the rest of the suite after b's stop, the driver's b
   tail -2 $O/pytest_rest.log
   grep -E "GiB/s end to end" $O/pytest_rest.log
   step driver-bench
-  timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err || { tail -20 $O/bench_driver_cmd.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err || { tail -20 $O/bench_driver_cmd.err; exit 1; }
   cat $O/bench_driver_cmd.json
   step copies
   timeout -k 10 300 python -u tools/probes/copy_pmc.py --copies 4 --per 4 > $O/copies.json 2> $O/copies.err || { tail -20 $O/copies.err; exit 1; }
@@ -87,7 +87,7 @@ if [ "$CALL" = g ]; then  # the tile passes timed by their dispatch packets: par
   timeout -k 10 500 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_host.py tests/test_gpu_fasta_tiles.py tests/test_gpu_line.py -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 1; }
   tail -1 $O/pytest.log
   step driver-bench
-  timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err || { tail -20 $O/bench_driver_cmd.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err || { tail -20 $O/bench_driver_cmd.err; exit 1; }
   python -c "import json;d=json.load(open('$O/bench_driver_cmd.json'));print(d['ms_per_step'],d['index_kernel_ms'],d['roofline']['frac'],d['build'],d['box_floor']['kernel_over_floor'])"
   step copies
   timeout -k 10 300 python -u tools/probes/copy_pmc.py --copies 4 --per 4 > $O/copies.json 2> $O/copies.err || { tail -20 $O/copies.err; exit 1; }

@@ -15,13 +15,13 @@ step() { echo "== $* ($(date +%T))"; }
 PART=${PART:-A}
 if [ "$PART" = F ]; then  # the FASTQ line alone (kernel sources changed after part A): trace, PMC, default bench
   rm -rf $O/prof_kt_fastq $O/prof_fetch_fastq $O/prof_write_fastq
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_kt_fastq -o kt --output-format csv -- python3 $R/bench.py --fmt fastq > $O/bench_kt_fastq.json 2> $O/bench_kt_fastq.err || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_kt_fastq -o kt --output-format csv -- python3 $R/bench.py --fmt fastq --full > $O/bench_kt_fastq.json 2> $O/bench_kt_fastq.err || exit 1
   timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d $O/prof_fetch_fastq -o pmc --output-format csv -- python3 $R/bench.py --fmt fastq --steps 3 --warmup 1 --cpu-sec 0 --no-check > /dev/null 2> $O/bench_fetch_fastq.err || exit 1
   timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE -d $O/prof_write_fastq -o pmc --output-format csv -- python3 $R/bench.py --fmt fastq --steps 3 --warmup 1 --cpu-sec 0 --no-check > /dev/null 2> $O/bench_write_fastq.err || exit 1
   python tools/pmc_summary.py $O/prof_kt_fastq $O/prof_fetch_fastq $O/prof_write_fastq $O/pmc_${TAG}_fastq.json fastq > $O/pmc_${TAG}_fastq.log 2>&1 || exit 1
   PMC_KERNEL=k_fq_place python tools/pmc_summary.py $O/prof_kt_fastq $O/prof_fetch_fastq $O/prof_write_fastq $O/pmc_${TAG}_k_fq_place.json fastq > $O/pmc_${TAG}_k_fq_place.log 2>&1 || exit 1
   mkdir -p profiles/$TAG && cp $O/pmc_${TAG}_fastq.json profiles/$TAG/pmc_fastq.json
-  timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err || exit 1
+  timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err || exit 1
   cat $O/bench_driver_cmd.json
   [ -n "$THEN_B" ] || exit 0
   PART=B
@@ -36,7 +36,7 @@ for FMT in fastq fasta; do
   step $FMT
   PK=$([ $FMT = fastq ] && echo k_fq_place || echo k_fa_place)
   rm -rf $O/prof_kt_$FMT $O/prof_fetch_$FMT $O/prof_write_$FMT
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_kt_$FMT -o kt --output-format csv -- python3 $R/bench.py --fmt $FMT > $O/bench_kt_$FMT.json 2> $O/bench_kt_$FMT.err || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_kt_$FMT -o kt --output-format csv -- python3 $R/bench.py --fmt $FMT --full > $O/bench_kt_$FMT.json 2> $O/bench_kt_$FMT.err || exit 1
   timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d $O/prof_fetch_$FMT -o pmc --output-format csv -- python3 $R/bench.py --fmt $FMT --steps 3 --warmup 1 --cpu-sec 0 --no-check > /dev/null 2> $O/bench_fetch_$FMT.err || exit 1
   timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE -d $O/prof_write_$FMT -o pmc --output-format csv -- python3 $R/bench.py --fmt $FMT --steps 3 --warmup 1 --cpu-sec 0 --no-check > /dev/null 2> $O/bench_write_$FMT.err || exit 1
   python tools/pmc_summary.py $O/prof_kt_$FMT $O/prof_fetch_$FMT $O/prof_write_$FMT $O/pmc_${TAG}_$FMT.json $FMT > $O/pmc_${TAG}_$FMT.log 2>&1 || exit 1
@@ -45,7 +45,7 @@ for FMT in fastq fasta; do
 done
 step line
 rm -rf $O/prof_kt_line $O/prof_fetch_line $O/prof_write_line
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_kt_line -o kt --output-format csv -- python3 $R/bench.py --kind line --cpu-sec 0 > $O/bench_line.json 2> $O/bench_line.err || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_kt_line -o kt --output-format csv -- python3 $R/bench.py --kind line --full --cpu-sec 0 > $O/bench_line.json 2> $O/bench_line.err || exit 1
 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d $O/prof_fetch_line -o pmc --output-format csv -- python3 $R/bench.py --kind line --steps 3 --warmup 1 --cpu-sec 0 --no-check > /dev/null 2> $O/fetch_line.err || exit 1
 timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE -d $O/prof_write_line -o pmc --output-format csv -- python3 $R/bench.py --kind line --steps 3 --warmup 1 --cpu-sec 0 --no-check > /dev/null 2> $O/write_line.err || exit 1
 for K in k_line_tiles k_line_place; do
@@ -63,9 +63,9 @@ done
 for f in fastq fasta; do for i in 1 2 3 4; do [ -d $O/sq_${f}_$i ] && KN=$([ $f = fastq ] && echo k_fq_tiles || echo k_fa_tiles) python tools/sq_table.py r06m/sq_${f}_$i; done; done > $O/sq_summary.txt 2>&1
 step default
 mkdir -p profiles/$TAG && cp $O/pmc_${TAG}_fastq.json profiles/$TAG/pmc_fastq.json && cp $O/pmc_${TAG}_fasta.json profiles/$TAG/pmc_fasta.json
-timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err || exit 1
+timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err || exit 1
 cat $O/bench_driver_cmd.json
-timeout -k 10 300 python -u bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
+timeout -k 10 300 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
 cat $O/bench_default.json
 exit 0
 fi
@@ -89,8 +89,8 @@ step filters
 for c in "fastq fq2fa" "fastq anonymize" "fasta anonymize"; do
   set -- $c
   rm -rf $O/filt_kt_$1_$2
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/filt_kt_$1_$2 -o run -- python3 bench.py --kind filter --fmt $1 --filter $2 --steps 5 --warmup 1 > $O/bench_filter_$1_$2.json 2> $O/bench_filter_$1_$2.err || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/filt_kt_$1_$2 -o run -- python3 bench.py --kind filter --fmt $1 --filter $2 --steps 5 --warmup 1 --full > $O/bench_filter_$1_$2.json 2> $O/bench_filter_$1_$2.err || exit 1
 done
 step rehearsal
-SHOCKIDX_BENCH_DEVICE=0 SHOCKIDX_BENCH_EXCHANGE=host timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 > $O/bench_rehearsal_2ranks_1gpu.json 2> $O/bench_rehearsal.err || exit 1
+SHOCKIDX_BENCH_DEVICE=0 SHOCKIDX_BENCH_EXCHANGE=host timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --full > $O/bench_rehearsal_2ranks_1gpu.json 2> $O/bench_rehearsal.err || exit 1
 exit 0
