@@ -27,6 +27,7 @@
 // next '\n' word and the previous success word in O(1).
 #include <hip/hip_runtime.h>
 #include "sidx_scan.hpp"
+#include "sidx_launch.hpp"
 
 #include <cstdint>
 

@@ -132,7 +132,6 @@ struct SlabParams {
   // (3 u16 per record, RCAP records per tile; sidx_filter.hip's spans come from them)
   uint16_t *fq_lines;
 };
-__device__ __forceinline__ bool gated_off(const SlabParams &p) { return p.gate && *p.gate != p.gate_fmt; }
 
 // Multi-GPU slab summary (mirrors shockidx_slab_summary in include/shockidx.h).
 // `seq` is the tag the caller gave the slab's build (shockidx_slab.seq): the fold refuses a
@@ -153,6 +152,13 @@ struct SlabPlan {
   u32 inconsistent, flags;
 };
 
+// DevResult::flags (also SlabSummary::flags and shockidx_result::flags)
+constexpr u32 RF_CAPACITY = 1;   // more rows than row_cap: `count` is exact, the rows are not all there
+constexpr u32 RF_INTERNAL = 2;   // a device invariant was violated
+constexpr u32 RF_HALO = 4;       // the slab's halo ended before a record could be closed (ST_NEEDMORE)
+constexpr u32 RF_FIXQUEUE = 8;   // the k_fixup queue overflowed: the host re-runs the two-pass build
+constexpr u32 RF_MISSPEC = 16;   // gated build: k_detect found another format than the speculated one
+
 // Device result of finalize (mirrored by shockidx_result in include/shockidx.h).
 struct DevResult {
   u64 count;       // records (rows) produced, Go's `count`
@@ -163,7 +169,7 @@ struct DevResult {
   u64 err_pos;     // FASTA error piece position (file offset)
   u64 err_len;     // FASTA error piece length
   u32 code;        // ST_* of the terminating record (0 / END / ABSENT = success)
-  u32 flags;       // bit0 capacity overflow, bit1 internal error, bit2 needmore
+  u32 flags;       // ResultFlag bits
   u32 path;        // set by the host: 1 tile pass, 2 two-pass build
   u32 fmt;         // format actually indexed
   u32 fixups;      // records / tiles queued for k_fixup (diagnostic)

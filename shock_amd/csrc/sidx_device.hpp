@@ -9,6 +9,9 @@
 
 namespace sidx {
 
+// format speculation (SlabParams::gate): the pipeline's kernels exit at once when this holds
+__device__ __forceinline__ bool gated_off(const SlabParams &p) { return p.gate && *p.gate != p.gate_fmt; }
+
 // ------------------------------------------------------------------------------------
 // SWAR: 16 bytes (one dwordx4) -> 16-bit mask of bytes equal to c (bit i = byte i)
 // ------------------------------------------------------------------------------------

@@ -24,6 +24,7 @@
 
 #include "sidx_common.hpp"
 #include "sidx_device.hpp"
+#include "sidx_launch.hpp"
 
 namespace sidx {
 

@@ -1,31 +1,178 @@
-// sidx_host.hpp -- host-side helpers of libshockidx shared between translation units
-// (defined in sidx_capi.cpp): staging of host bytes into a context's HBM input buffer and the
-// table copy-out through its pinned staging buffers, Go's status texts.  Internal: not part
-// of the C ABI (include/shockidx.h).
+// sidx_host.hpp -- the host side of libshockidx as its translation units see each other: the
+// context, the error helpers, and the functions of sidx_build.cpp (workspaces, one index pass,
+// staging, copy-out) and sidx_pipeline.cpp (the slab pipelines) that the entry points call.
+// Internal: not part of the C ABI (include/shockidx.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
+
+#include <chrono>
+#include <condition_variable>
+#include <functional>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
 
 #include "../../include/shockidx.h"
+#include "sidx_common.hpp"
 
 namespace sidx_host {
 
-double now_ms();
+constexpr size_t STAGE_BYTES = 64ull << 20;  // pinned staging chunk
+constexpr int NSTAGE = 2;
+// c->d_small: badkey slots at +0/+8, counter slots at +64/+80
+constexpr size_t SMALL_BADKEY = 0, SMALL_COUNTERS = 64, SMALL_RESULT = 128, SMALL_DETECT = 320, SMALL_CHUNK = 384,
+                 SMALL_SLABSUM = 448, SMALL_BYTES = 512;
+
+inline double now_ms() {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// Host copies between the caller's memory and the pinned staging buffers, split over a
+// small persistent thread pool (one memcpy thread tops out near 25 GB/s, below PCIe Gen5).
+class CopyPool {
+ public:
+  explicit CopyPool(int n);
+  ~CopyPool();
+  void copy(void *dst, const void *src, size_t n);
+  // f(a, b) over disjoint 4 KiB-aligned slices of [0, n), one per thread (small n: inline)
+  void parallel(size_t n, const std::function<void(size_t, size_t)> &f);
+
+ private:
+  void run(int i);
+  const int nt_;
+  std::vector<std::thread> th_;
+  std::mutex m_;
+  std::condition_variable cv_, done_;
+  const std::function<void(size_t, size_t)> *fn_ = nullptr;
+  size_t n_ = 0;
+  int pending_ = 0;
+  unsigned long long gen_ = 0;
+  bool stop_ = false;
+};
+
+}  // namespace sidx_host
+
+struct shockidx_ctx {
+  typedef sidx::u64 u64;
+  typedef sidx::u32 u32;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, ek0 = nullptr, ek1 = nullptr;
+  hipEvent_t stage_ev[sidx_host::NSTAGE] = {nullptr, nullptr};
+  uint8_t *d_in = nullptr;
+  u64 d_in_cap = 0;
+  u64 *d_rows = nullptr;
+  u64 d_rows_cap = 0;  // rows
+  u64 *d_status = nullptr;
+  u64 *d_detail = nullptr;
+  u64 *d_fix = nullptr;  // k_fixup queue (FixRec, 32 bytes each), tiles_cap items
+  u64 tiles_cap = 0;
+  uint8_t *d_small = nullptr;  // badkey[2] | counters[2][NCOUNTERS] | result | detect
+  u32 epoch = 0;               // build epoch for the look-back words (1..EPOCH_MASK)
+  bool slots_dirty = false;    // a build took an epoch and did not reach its finalize
+  int spec_fmt = 0;            // the last detected format (speculated by the next AUTO build)
+  u64 *d_timing = nullptr;     // diagnostic phase timing buffer (SHOCKIDX_TIMING)
+  u32 tiles_grid = 0;               // persistent grid of the tile passes (CUs x co-resident)
+  uint8_t *h_stage[sidx_host::NSTAGE] = {nullptr, nullptr};
+  sidx::DevResult *h_res = nullptr;
+  sidx_host::CopyPool *pool = nullptr;  // host memcpy threads for the host-memory entry points
+  uint8_t *d_sub = nullptr;        // subset / gather workspace
+  u64 d_sub_cap = 0;
+  int *h_det = nullptr;
+  u64 ws_cap = 0;                  // SHOCKIDX_WORKSPACE_CAP: trim the caches above this after a call
+  u64 dev_cap = 0;                 // device bytes a build may hold (0: what the device has free;
+                                   //   shockidx_ctx_set_dev_cap / SHOCKIDX_DEV_CAP)
+  u32 *d_fqstage = nullptr;        // FASTQ tile pass: provisional rows (TILE / 64 per tile)
+  u64 fqstage_cap = 0;             //   (u32 entries)
+  u32 *d_fqtiles = nullptr;        //   per-tile results (FQ_TILE_WORDS per tile)
+  u64 fqtiles_cap = 0;
+  uint8_t *d_cra = nullptr;        // speculative chunkrecord: FASTQ record table / FASTA tile counts
+  u64 cra_cap = 0;                 //   (bytes)
+  uint8_t *d_crb = nullptr;        //   node positions, jump tables, path, results (bytes)
+  uint8_t *d_slot[2] = {nullptr, nullptr};  // fd builds within the device cap: the two slab slots
+  u64 slot_cap = 0;                //   (bytes each)
+  u64 crb_cap = 0;
+  u32 cr_grid = 0;                 //   k_cr_verify persistent grid
+  hipStream_t s_copy = nullptr;    // slab-pipelined host builds: the H2D stream
+  uint8_t *h_rows[2] = {nullptr, nullptr};  // slab-pipelined fd builds: pinned row staging (D2H)
+  // download filters over FASTQ: the tile pass keeps each record's line ends (k_fq_tiles<true>)
+  bool want_spans = false;
+  uint16_t *d_fqlines = nullptr;
+  u64 fqlines_cap = 0;             //   (u16 entries)
+  sidx::SlabParams last_p;         // the last FASTQ tile pass's parameters (k_fq_spans_place)
+  bool last_spans = false;         //   its line ends are in d_fqlines
+  // test hooks (shockidx_debug_inject, not in the public header): bit0 a freshly grown status
+  // array is filled with published words of the next build's epoch before it is zeroed, bit1
+  // after it is zeroed (what a zeroing that lost a race with the build would leave), bit2 the
+  // finalize reports one record short
+  u32 inject = 0;
+};
+
+namespace sidx_host {
+
+// ---- results and errors ----------------------------------------------------------------------
 int set_msg(shockidx_result *r, int code, const char *msg);
 int set_hip(shockidx_result *r, hipError_t e, const char *what);
+inline void reset_result(shockidx_result *r) {
+  if (r) memset(r, 0, sizeof *r);
+}
 // Go's text for a FASTQ status code (ST_*), nullptr for codes without one
 const char *status_message(uint32_t code);
 
-int ctx_device(shockidx_ctx *c);
-hipStream_t ctx_stream(shockidx_ctx *c);
-// Bytes [off, off + len) of a host buffer (src) or of a file (src null: fd) into the context's
-// input buffer (grown as needed, 16-byte aligned); *d_out = its device address.
-int ctx_stage(shockidx_ctx *c, const void *src, int fd, uint64_t off, uint64_t len, const uint8_t **d_out,
-              shockidx_result *res);
-// bytes of device memory (on the context's device) into host memory through pinned staging
-int ctx_to_host(shockidx_ctx *c, const void *d_src, uint64_t bytes, void *dst, shockidx_result *res);
-// a row table the caller frees with free() / shockidx_free (2 MiB aligned when large)
-uint64_t *alloc_rows(uint64_t bytes);
+#define HIPCHK(expr, what)                      \
+  do {                                          \
+    hipError_t _e = (expr);                     \
+    if (_e != hipSuccess) return sidx_host::set_hip(res, _e, what); \
+  } while (0)
+
+// fasta.go:115-121: fmt.Errorf("Invalid fasta entry: %s", read[0:min(50, len(read))]) into res;
+// read_piece(dst, k) fetches the piece's first k bytes (0, or its error code with res set).
+template <class Read>
+int fasta_error_text(shockidx_result *res, uint64_t err_len, Read read_piece) {
+  static const char pre[] = "Invalid fasta entry: ";
+  const uint64_t show = err_len < 50 ? err_len : 50;
+  memcpy(res->err, pre, sizeof pre - 1);
+  if (show)
+    if (int rc = read_piece(res->err + sizeof pre - 1, show)) return rc;
+  res->err_len = sizeof pre - 1 + show;
+  res->err[res->err_len] = 0;
+  res->status = SHOCKIDX_EFORMAT;
+  return SHOCKIDX_EFORMAT;
+}
+
+// the subset / filter entry points' result (shockidx_subset_result)
+inline void sub_reset(shockidx_subset_result *r) { memset(r, 0, sizeof *r); }
+int sub_msg(shockidx_subset_result *r, int code, const std::string &m);
+int sub_hip(shockidx_subset_result *r, hipError_t e, const char *what);
+#define SUBCHK(expr, what)                                 \
+  do {                                                     \
+    hipError_t _e = (expr);                                \
+    if (_e != hipSuccess) return sidx_host::sub_hip(res, _e, what);   \
+  } while (0)
+
+// carve 256-byte-aligned pieces out of a device workspace
+struct Carver {
+  uint8_t *base;
+  sidx::u64 off = 0;
+  template <class T> T *take(sidx::u64 n) {
+    T *p = (T *)(base + off);
+    off += (n * sizeof(T) + 255) / 256 * 256;
+    return p;
+  }
+};
+
+// one T from device memory, waited for
+template <class T>
+int d2h(shockidx_ctx *c, T *dst, const void *src, shockidx_subset_result *res) {
+  SUBCHK(hipMemcpyAsync(dst, src, sizeof(T), hipMemcpyDeviceToHost, c->stream), "subset copy");
+  SUBCHK(hipStreamSynchronize(c->stream), "subset sync");
+  return 0;
+}
+
+// ---- device memory and the context's caches (sidx_build.cpp) ---------------------------------
 // Device memory; node = a node body the tile passes stream (the context's input staging,
 // shockidx_dev_alloc_node): physically contiguous when the driver can (hipDeviceMallocContiguous),
 // else plain hipMalloc.  10 GiB FASTQ, interleaved allocations in one process on MI355X:
@@ -34,5 +181,91 @@ uint64_t *alloc_rows(uint64_t bytes);
 // profiles/r04/placement2b.txt).  Written buffers (row tables, tile words) stay plain: the row
 // placement ran 0.13 -> 0.18 ms into contiguous memory.  Freed with hipFree.
 hipError_t dev_malloc(void **p, size_t bytes, bool node);
+// grow-only: *p holds at least `need` elements of `elem` bytes afterwards
+int ensure_dev(shockidx_ctx *c, void **p, sidx::u64 *cap, sidx::u64 need, size_t elem, shockidx_result *res,
+               bool node = false);
+// device bytes held by the context's grow-only caches
+sidx::u64 workspace_bytes(const shockidx_ctx *c);
+// free the large caches (they regrow on demand); the tile status words go only with keep = 0
+void trim_workspace(shockidx_ctx *c, sidx::u64 keep);
+// trims the caches to the context's cap when a host-facing call returns
+struct TrimGuard {
+  shockidx_ctx *c;
+  ~TrimGuard() {
+    if (c && c->ws_cap) trim_workspace(c, c->ws_cap);
+  }
+};
+// Device bytes a build may hold: the context's cap, and never more than the device has free plus
+// what this context already holds
+sidx::u64 dev_budget(shockidx_ctx *c);
+// what a one-pass build of an n-byte node holds at its peak
+sidx::u64 one_pass_bytes(sidx::u64 n);
+
+// ---- one index pass (sidx_build.cpp) ---------------------------------------------------------
+// Slab geometry of one index pass (a single-GPU build is one slab = the whole file).
+struct SlabGeom {
+  sidx::u64 n, end, front, base, state_in, row_base;
+  int eof, file_start;
+  void *d_summary;
+  sidx::u32 seq = 0;  // the summary's build tag (shockidx_slab.seq)
+};
+int resolve_format(shockidx_ctx *c, const uint8_t *d_data, sidx::u64 n, int kind, int fmt, hipStream_t s, int *kfmt,
+                   shockidx_result *res, const int **gate = nullptr);
+int respeculate(shockidx_ctx *c, const sidx::DevResult &dr, int *kfmt, shockidx_result *res);
+int run_index(shockidx_ctx *c, const uint8_t *d_data, sidx::u64 n, int kfmt, sidx::u64 *d_rows, sidx::u64 row_cap,
+              hipStream_t s, sidx::DevResult *dr, shockidx_result *res, const SlabGeom *geom = nullptr,
+              bool general = false, const int *gate = nullptr);
+int translate(shockidx_ctx *c, const sidx::DevResult &dr, const uint8_t *d_data, hipStream_t s, shockidx_result *res);
+int build_resident(shockidx_ctx *c, const uint8_t *d_data, sidx::u64 n, int kind, int fmt, hipStream_t s,
+                   shockidx_result *res);
+
+// ---- staging and copy-out (sidx_build.cpp) ---------------------------------------------------
+// a row table the caller frees with free() / shockidx_free (2 MiB aligned when large)
+uint64_t *alloc_rows_out(size_t bytes);
+int rows_to_host(shockidx_ctx *c, const sidx::u64 *d_src, size_t bytes, uint8_t *dst, hipStream_t s,
+                 shockidx_result *res);
+int fetch_rows(shockidx_ctx *c, sidx::u64 count, hipStream_t s, uint64_t **rows, shockidx_result *res);
+// Host memory the GPU can DMA from directly (hipHostRegister'ed or hipHostMalloc'ed)
+bool host_pinned(const void *p, sidx::u64 n);
+// n bytes of pageable host memory / file bytes [off, off + n) into c->d_in (grown as needed)
+int stage_host(shockidx_ctx *c, const void *data, sidx::u64 n, hipStream_t s, shockidx_result *res);
+int stage_fd(shockidx_ctx *c, int fd, sidx::u64 off, sidx::u64 n, hipStream_t s, shockidx_result *res);
+// Host bytes of a file for the pinned staging: pread until every byte of [off, off + k) has arrived
+// (Linux returns at most 0x7ffff000 bytes per call; short reads and EINTR are retried).
+struct PreadFill {
+  int fd;
+  shockidx_result *res;
+  CopyPool *pool;  // slices of each staging chunk are read by the pool's threads in parallel
+  int operator()(uint8_t *dst, sidx::u64 off, size_t k) const;
+};
+// the process-wide budget of pinned page-cache bytes (pin_cap()): reserve before hipHostRegister,
+// release after unregistering
+bool pin_reserve(sidx::u64 b);
+void pin_release(sidx::u64 b);
+
+// ---- the slab pipelines (sidx_pipeline.cpp) --------------------------------------------------
+// Where the rows of a slab-pipelined fd build go, as each slab's rows arrive in pinned host
+// memory (called from the pipeline's index thread, rows in file order): the caller's table
+// (shockidx_build_fd) or the temp .idx file (shockidx_create, pwrite at 16 * first row).
+struct RowSink {
+  virtual ~RowSink() {}
+  virtual int put(const uint8_t *src, sidx::u64 first, sidx::u64 nrows, shockidx_result *res) = 0;
+};
+struct TableSink : RowSink {  // a malloc'ed table, grown as rows arrive (the caller frees it)
+  uint8_t *out = nullptr;
+  size_t cap = 0;
+  explicit TableSink(sidx::u64 n);
+  ~TableSink() override;
+  int put(const uint8_t *src, sidx::u64 first, sidx::u64 nrows, shockidx_result *res) override;
+};
+struct FileSink : RowSink {  // the .idx temp file: rows are {u64 off, u64 len} LE (record.go:74-75)
+  int fd = -1;
+  int put(const uint8_t *src, sidx::u64 first, sidx::u64 nrows, shockidx_result *res) override;
+};
+// *done = false: not applicable, the caller runs the plain path
+int build_host_pipelined(shockidx_ctx *c, const void *data, sidx::u64 n, int kind, int fmt, uint64_t **rows,
+                         shockidx_result *res, bool *done);
+int build_fd_pipelined(shockidx_ctx *c, int fd, sidx::u64 n, int kind, int fmt, RowSink &sink, shockidx_result *res,
+                       bool *done, bool *fell_back);
 
 }  // namespace sidx_host

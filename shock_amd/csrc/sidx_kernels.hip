@@ -23,6 +23,7 @@
 
 #include "sidx_common.hpp"
 #include "sidx_device.hpp"
+#include "sidx_launch.hpp"
 #include <stdlib.h>
 #include <string.h>
 
@@ -2837,7 +2838,7 @@ __global__ void k_finalize(const SlabParams p, int fmt, DevResult *res) {
 __device__ __forceinline__ void finalize_body(const SlabParams &p, int fmt, DevResult *res) {
   if (gated_off(p)) {  // the speculated format was wrong: nothing ran; the host re-runs
     DevResult r = {};
-    r.flags = 16;
+    r.flags = RF_MISSPEC;
     r.fmt = (u32)fmt;
     r.detected = (u32)*p.gate;
     *res = r;
@@ -2866,7 +2867,7 @@ __device__ __forceinline__ void finalize_body(const SlabParams &p, int fmt, DevR
   r.detected = p.gate ? (u32)*p.gate : 0u;
   r.pad = 0;
   r.key = key;
-  if ((w >> 62) != 2 || (((u32)(w >> EPOCH_SHIFT)) & EPOCH_MASK) != p.epoch) r.flags |= 2;  // no final INC
+  if ((w >> 62) != 2 || (((u32)(w >> EPOCH_SHIFT)) & EPOCH_MASK) != p.epoch) r.flags |= RF_INTERNAL;  // no final INC
   u64 krec = key >> KEY_REC_SHIFT;
   u32 kst = (u32)(key & 15);
   const u32 ktile = (u32)((key >> 4) & ((1u << KEY_TILE_BITS) - 1));
@@ -2886,20 +2887,20 @@ __device__ __forceinline__ void finalize_body(const SlabParams &p, int fmt, DevR
       r.err_pos = p.detail[2 * (u64)ktile];
       r.err_len = p.detail[2 * (u64)ktile + 1];
     }
-    if (kst == ST_DONTCARE) r.flags |= 2;
-    if (kst == ST_NEEDMORE) r.flags |= 4;
+    if (kst == ST_DONTCARE) r.flags |= RF_INTERNAL;
+    if (kst == ST_NEEDMORE) r.flags |= RF_HALO;
   }
-  if (p.counters[1]) r.flags |= 2;
-  if (p.counters[3] & 1) r.flags |= 8;  // k_fixup queue overflow: re-run on the general kernel
+  if (p.counters[1]) r.flags |= RF_INTERNAL;
+  if (p.counters[3] & 1) r.flags |= RF_FIXQUEUE;  // k_fixup queue overflow: re-run on the general kernel
   if (p.inject & 1) r.count = r.count ? r.count - 1 : 0;  // test hook: a short count
   const u64 nrows = r.count > p.row_base ? r.count - p.row_base : 0;
-  if (nrows > p.row_cap) r.flags |= 1;
+  if (nrows > p.row_cap) r.flags |= RF_CAPACITY;
   // End-of-build invariants of a whole-file build (record.go:51-83: row i + 1 starts where row i
   // ends, the first at 0).  A successful FASTA / SAM / line build consumes every byte, so its last
   // row ends at the file end; a FASTQ build only skips trailing blank lines after its last record
   // (fastq.go:141-156).  A build whose count or rows came out of stale device state fails here
   // and reports an internal error instead of a short table.
-  if (p.file_start && p.eof && p.end == p.n && !(r.flags & 9) && nrows && p.rows) {  // (p.end > p.n: a slab's halo)
+  if (p.file_start && p.eof && p.end == p.n && !(r.flags & (RF_CAPACITY | RF_FIXQUEUE)) && nrows && p.rows) {  // (p.end > p.n: a slab's halo)
     const u64 *rw = p.rows;
     bool bad = rw[0] != p.base;
     if (r.code == ST_OK || r.code == ST_END || r.code == ST_ABSENT) {
@@ -2909,7 +2910,7 @@ __device__ __forceinline__ void finalize_body(const SlabParams &p, int fmt, DevR
       // the line index's last row is the bytes after the last '\n' (line.go:37-45, possibly none)
       if (fmt == F_LINE) bad |= rw[2 * (nrows - 1) + 1] != 0 && p.n && p.data[p.n - 1] == '\n';
     }
-    if (bad) r.flags |= 2;
+    if (bad) r.flags |= RF_INTERNAL;
   }
   *res = r;
   if (p.summary) {
@@ -3049,7 +3050,7 @@ __device__ void slab_combine(const SlabSummary *all, int world, int rank, const 
     if (!ok) pl.inconsistent |= 1u << q;
     const u64 delta = slab_delta<F>(s, x.state_in);
     if (q == rank) { pl.state_in = s; pl.first_record = delta + x.row_base; }
-    pl.flags |= x.flags & ~1u;
+    pl.flags |= x.flags & ~RF_CAPACITY;
     if (!done && ok) {
       if (x.key != KEY_NONE) {
         pl.count = (x.key >> KEY_REC_SHIFT) + delta;
@@ -3383,7 +3384,7 @@ extern "C" hipError_t sidx_launch_slab_combine(const void *d_all, int world, int
 // read on the device after the pipeline); a violation sets the internal-error flag.
 __global__ __launch_bounds__(256) void k_verify_rows(const u64 *rows, u64 row_base, u64 row_cap, DevResult *res) {
   const DevResult r = *res;
-  if (r.flags & 17) return;  // a capacity overflow or a failed speculation: re-run anyway
+  if (r.flags & (RF_CAPACITY | RF_MISSPEC)) return;  // a capacity overflow or a failed speculation: re-run anyway
   const u64 nr = r.count > row_base ? r.count - row_base : 0;
   const u64 n = nr < row_cap ? nr : row_cap;
   bool bad = false;
@@ -3391,7 +3392,7 @@ __global__ __launch_bounds__(256) void k_verify_rows(const u64 *rows, u64 row_ba
     const ulonglong2 a = reinterpret_cast<const ulonglong2 *>(rows)[i];
     bad |= a.x + a.y != rows[2 * (i + 1)];
   }
-  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&res->flags, 2u);
+  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&res->flags, RF_INTERNAL);
 }
 extern "C" hipError_t sidx_launch_verify_rows(const u64 *rows, u64 row_base, u64 row_cap, DevResult *d_res, hipStream_t s) {
   hipLaunchKernelGGL(k_verify_rows, dim3(1024), dim3(256), 0, s, rows, row_base, row_cap, d_res);

@@ -1,0 +1,103 @@
+// sidx_launch.hpp -- every kernel launcher and query that crosses from a .hip file to host code.
+//
+// Included by the host files that call them and by the .hip file that defines each, so a
+// definition that drifts from its prototype is a compile error ("conflicting types"), not
+// garbage arguments at run time.  The one declaration of each function in the tree.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "sidx_common.hpp"
+
+extern "C" {
+
+hipError_t sidx_launch_detect(const uint8_t *d, sidx::u64 n, int *d_out, hipStream_t s);
+hipError_t sidx_launch_index(int fmt, const sidx::SlabParams *p, sidx::DevResult *d_res, hipStream_t s,
+    hipEvent_t ek0, hipEvent_t ek1);
+hipError_t sidx_launch_chunkrecord(const uint8_t *d, sidx::u64 n, int fasta, long long chunk, sidx::u64 *rows,
+    sidx::u64 row_cap, sidx::u64 *out, long long curr0, sidx::u64 cnt0, sidx::u64 max_steps, hipStream_t s);
+hipError_t sidx_cr_gpos_count(const uint8_t *d, sidx::u64 n, sidx::u64 *tcnt, sidx::u64 *toff, uint16_t *slot,
+    void *scan_tmp, size_t *scan_bytes, hipStream_t s);
+hipError_t sidx_cr_gpos_write(const uint8_t *d, sidx::u64 n, const sidx::u64 *tcnt, const sidx::u64 *toff,
+    const uint16_t *slot, sidx::u64 *G, hipStream_t s);
+sidx::u32 sidx_cr_gslot();
+hipError_t sidx_cr_graph(const uint8_t *d, sidx::u64 n, int fasta, sidx::u64 chunk, const sidx::u64 *base,
+    sidx::u64 stride, sidx::u64 count, sidx::u64 *ft, sidx::u32 *J1, sidx::u32 *Ja, sidx::u32 *Jb, int levels,
+    const sidx::u32 **JL, hipStream_t s);
+hipError_t sidx_cr_round(const uint8_t *d, sidx::u64 n, int fasta, sidx::u64 chunk, const sidx::u64 *base,
+    sidx::u64 stride, sidx::u64 count, const sidx::u64 *ft, const sidx::u32 *JL, const sidx::u32 *J1, sidx::u32 L,
+    sidx::u64 y, sidx::u64 k0, sidx::u64 cap, sidx::u32 *heads, sidx::u64 *pos, sidx::i64 *mres, sidx::u64 *ctl,
+    sidx::u64 *rows, sidx::u64 row_cap, sidx::u32 verify_grid, hipStream_t s);
+int sidx_cr_verify_blocks_per_cu();
+sidx::u32 sidx_fa_slot();
+hipError_t sidx_fa_bnd_count(const uint8_t *d, sidx::u64 n, sidx::u64 *lnl, sidx::u64 *lgt, sidx::u64 *cnl,
+    sidx::u64 *cgt, sidx::u64 *tcnt, sidx::u64 *toff, uint16_t *slot, void *tmp, size_t *tmp_bytes, hipStream_t s);
+hipError_t sidx_fa_bnd_write(const uint8_t *d, sidx::u64 n, const sidx::u64 *cnl, const sidx::u64 *cgt,
+    const sidx::u64 *tcnt, const sidx::u64 *toff, const uint16_t *slot, sidx::u64 *B, hipStream_t s);
+hipError_t sidx_fa_anon_spans(const uint8_t *d, sidx::u64 n, const sidx::u64 *B, sidx::u64 bstride, sidx::u64 m,
+    sidx::u64 *bspan, sidx::u64 *outlen, sidx::u64 *firstbad, hipStream_t s);
+hipError_t sidx_fa_anon_write(const uint8_t *d, sidx::u64 n, const sidx::u64 *bspan, const sidx::u64 *outoff,
+    sidx::u64 K, uint8_t *out, hipStream_t s);
+hipError_t sidx_sam_anon_spans(const uint8_t *d, sidx::u64 n, const sidx::u64 *rows, sidx::u64 K, sidx::u64 *span,
+    sidx::u64 *outlen, sidx::u64 *firstbad, sidx::u64 *firsteof, hipStream_t s);
+hipError_t sidx_sam_anon_write(const uint8_t *d, const sidx::u64 *span, const sidx::u64 *outlen,
+    const sidx::u64 *outoff, sidx::u64 K, uint8_t *out, sidx::u64 *count, hipStream_t s);
+hipError_t sidx_crs_scan(const sidx::u64 *ri, sidx::u64 R, sidx::u64 *len, sidx::u64 *P, void *tmp,
+    size_t *scan_bytes, hipStream_t s);
+hipError_t sidx_crs_build(const sidx::u64 *P, sidx::u64 R, sidx::u32 *J1, sidx::u32 *Ja, sidx::u32 *Jb, int levels,
+    sidx::u32 *heads, sidx::u64 *rows, sidx::u64 row_cap, sidx::u64 *ctl, hipStream_t s);
+int sidx_tiles_blocks_per_cu();
+hipError_t sidx_launch_slab_guess(const uint8_t *d, sidx::u64 n, sidx::u64 front, int fmt, sidx::u64 *d_out,
+    hipStream_t s);
+hipError_t sidx_launch_verify_rows(const sidx::u64 *rows, sidx::u64 row_base, sidx::u64 row_cap,
+    sidx::DevResult *d_res, hipStream_t s);
+hipError_t sidx_launch_slab_combine(const void *d_all, int world, int rank, int fmt, const uint32_t *expect,
+    void *d_plan, hipStream_t s);
+hipError_t sidx_id_lines(const uint8_t *text, sidx::u64 n, sidx::u32 *cnt, sidx::u64 *base, sidx::u64 *ends,
+    void *tmp, size_t *tmp_bytes, hipStream_t s);
+hipError_t sidx_subset_parse(const uint8_t *text, const sidx::u64 *ends, sidx::u64 m, sidx::u32 *keep,
+    sidx::i64 *val, sidx::u32 *st, hipStream_t s);
+hipError_t sidx_scan_flags(const sidx::u32 *in, sidx::u64 *out, sidx::u64 n, void *tmp, size_t *tmp_bytes,
+    hipStream_t s);
+hipError_t sidx_scan_u64(const sidx::u64 *in, sidx::u64 *out, sidx::u64 n, void *tmp, size_t *tmp_bytes,
+    hipStream_t s);
+hipError_t sidx_subset_compact(const sidx::u32 *keep, const sidx::u64 *rank, const sidx::i64 *val,
+    const sidx::u32 *st, sidx::u64 m, sidx::i64 *cval, sidx::u32 *cst, sidx::u64 *cline, sidx::u64 *ctl,
+    hipStream_t s);
+hipError_t sidx_subset_init(sidx::u64 *ctl, sidx::u64 nruns, hipStream_t s);
+hipError_t sidx_subset_check(const sidx::i64 *cval, const sidx::u32 *cst, sidx::u64 m, sidx::u64 *ctl,
+    const sidx::u64 *parent, sidx::u64 parent_count, sidx::i64 ilength, sidx::u64 *rows, sidx::u64 rows_cap,
+    sidx::u32 *startf, hipStream_t s);
+hipError_t sidx_subset_runs(const sidx::u64 *rows, const sidx::u32 *startf, const sidx::u64 *runid, sidx::u64 m,
+    sidx::u64 *ctl, sidx::u64 *runs, sidx::u64 rows_cap, sidx::u64 runs_cap, hipStream_t s);
+hipError_t sidx_launch_fq_spans_place(const sidx::SlabParams *pp, sidx::u32 *spans, sidx::u64 *outlen, sidx::u64 K,
+    int kind, hipStream_t s);
+hipError_t sidx_launch_fq_tiles(const sidx::SlabParams *pp, sidx::DevResult *d_res, hipStream_t s, hipEvent_t ek0,
+    hipEvent_t ek1);
+hipError_t sidx_launch_fa_tiles(const sidx::SlabParams *pp, sidx::DevResult *d_res, hipStream_t s, hipEvent_t ek0,
+    hipEvent_t ek1);
+int sidx_fa_tiles();
+hipError_t sidx_launch_line_tiles(const sidx::SlabParams *pp, sidx::DevResult *d_res, hipStream_t s, hipEvent_t ek0,
+    hipEvent_t ek1);
+int sidx_line_tiles();
+hipError_t sidx_launch_sam_tiles(const sidx::SlabParams *pp, sidx::DevResult *d_res, hipStream_t s, hipEvent_t ek0,
+    hipEvent_t ek1);
+int sidx_sam_tiles();
+hipError_t sidx_filter_spans(const uint8_t *data, sidx::u64 n, const sidx::u64 *rows, sidx::u64 K, int kind,
+    sidx::u32 *spans, sidx::u64 *outlen, sidx::u64 *firstbad, hipStream_t s);
+hipError_t sidx_filter_write(const uint8_t *data, sidx::u64 n, const sidx::u64 *rows, const sidx::u32 *spans,
+    const sidx::u64 *outlen, const sidx::u64 *outoff, sidx::u64 K, sidx::u64 total, int kind, sidx::u64 *wfirst,
+    uint8_t *out, hipStream_t s);
+sidx::u64 sidx_filter_block();
+hipError_t sidx_filter_read_status(const uint8_t *data, sidx::u64 n, sidx::u64 start, sidx::u32 *out,
+    hipStream_t s);
+hipError_t sidx_range_flags(const sidx::u64 *rows, sidx::u64 nrows, sidx::u64 a0, sidx::u64 nr, sidx::u32 *flags,
+    hipStream_t s);
+hipError_t sidx_range_emit(const sidx::u64 *rows, sidx::u64 nrows, sidx::u64 a0, sidx::u64 nr,
+    const sidx::u32 *flags, const sidx::u64 *id, sidx::u64 *recs, hipStream_t s);
+hipError_t sidx_gather(const uint8_t *data, sidx::u64 data_len, const sidx::u64 *runs, sidx::u64 bound,
+    sidx::u64 *ctl, sidx::u64 *lens, sidx::u64 *outoff, void *tmp, size_t *tmp_bytes, sidx::u64 *wfirst,
+    uint8_t *out, sidx::u64 out_cap, hipEvent_t e0, hipEvent_t e1, hipStream_t s);
+
+}  // extern "C"

@@ -32,7 +32,12 @@
 #include "../../include/shockidx.h"
 #include "sidx_host.hpp"
 
-using namespace sidx_host;
+using sidx_host::alloc_rows_out;
+using sidx_host::fasta_error_text;
+using sidx_host::now_ms;
+using sidx_host::set_hip;
+using sidx_host::set_msg;
+using sidx_host::status_message;
 
 namespace {
 
@@ -118,7 +123,7 @@ int exchange(shockidx_multi *m, shockidx_result *res) {
   if (!m->comm.empty()) {  // one RCCL all-gather of 64 B per device over xGMI
     if (ncclGroupStart() != ncclSuccess) return set_msg(res, SHOCKIDX_EHIP, "ncclGroupStart");
     for (int k = 0; k < n; ++k) {
-      if (ncclAllGather(m->d_sum[k], m->d_sum[k] + 64, 64, ncclUint8, m->comm[k], ctx_stream(m->ctx[k])) !=
+      if (ncclAllGather(m->d_sum[k], m->d_sum[k] + 64, 64, ncclUint8, m->comm[k], m->ctx[k]->stream) !=
           ncclSuccess) {
         (void)ncclGroupEnd();
         return set_msg(res, SHOCKIDX_EHIP, "ncclAllGather");
@@ -127,7 +132,7 @@ int exchange(shockidx_multi *m, shockidx_result *res) {
     if (ncclGroupEnd() != ncclSuccess) return set_msg(res, SHOCKIDX_EHIP, "ncclGroupEnd");
     for (int k = 0; k < n; ++k) {
       hipError_t e = hipSetDevice(m->dev[k]);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx_stream(m->ctx[k]));
+      if (e == hipSuccess) e = hipStreamSynchronize(m->ctx[k]->stream);
       if (e != hipSuccess) return set_hip(res, e, "all-gather sync");
     }
     return 0;
@@ -139,14 +144,14 @@ int exchange(shockidx_multi *m, shockidx_result *res) {
   std::vector<uint8_t> all(64 * (size_t)n);
   if (m->inject & 1) return 0;  // test hook: the gathered buffers keep what the last exchange left
   for (int k = 0; k < n; ++k) {
-    hipStream_t s = ctx_stream(m->ctx[k]);
+    hipStream_t s = m->ctx[k]->stream;
     hipError_t e = hipSetDevice(m->dev[k]);
     if (e == hipSuccess) e = hipMemcpyAsync(all.data() + 64 * k, m->d_sum[k], 64, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return set_hip(res, e, "summary copy");
   }
   for (int k = 0; k < n; ++k) {
-    hipStream_t s = ctx_stream(m->ctx[k]);
+    hipStream_t s = m->ctx[k]->stream;
     hipError_t e = hipSetDevice(m->dev[k]);
     if (e == hipSuccess) e = hipMemcpyAsync(m->d_sum[k] + 64, all.data(), all.size(), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -289,17 +294,8 @@ int finish_status(const shockidx_slab_plan &p, shockidx_result *res, Fetch fetch
     res->status = SHOCKIDX_OK;
     return SHOCKIDX_OK;
   }
-  if (p.code == ST_FA_INVALID) {  // fasta.go:115-121
-    static const char pre[] = "Invalid fasta entry: ";
-    const u64 show = p.err_len < 50 ? p.err_len : 50;
-    memcpy(res->err, pre, sizeof pre - 1);
-    if (show)
-      if (int rc = fetch(p.err_pos, show, (uint8_t *)res->err + sizeof pre - 1)) return rc;
-    res->err_len = sizeof pre - 1 + show;
-    res->err[res->err_len] = 0;
-    res->status = SHOCKIDX_EFORMAT;
-    return SHOCKIDX_EFORMAT;
-  }
+  if (p.code == ST_FA_INVALID)
+    return fasta_error_text(res, p.err_len, [&](char *dst, u64 k) -> int { return fetch(p.err_pos, k, (uint8_t *)dst); });
   const char *msg = status_message(p.code);
   if (!msg) return set_msg(res, SHOCKIDX_EINTERNAL, "internal error: unknown status");
   return set_msg(res, SHOCKIDX_EFORMAT, msg);
@@ -318,6 +314,23 @@ int resolve_fmt(shockidx_multi *m, const uint8_t *head, u64 hn, int kind, int fm
     return set_msg(res, SHOCKIDX_EINVAL, "invalid format");
   *out = fmt;
   return 0;
+}
+
+// Bytes [off, off + len) of a host buffer (src) or of a file (src null: fd) into the context's
+// input buffer (grown as needed, 16-byte aligned); *d_out = its device address.
+int stage_window(shockidx_ctx *c, const void *src, int fd, u64 off, u64 len, const uint8_t **d_out, shockidx_result *res) {
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  const int rc = src ? sidx_host::stage_host(c, (const uint8_t *)src + off, len, c->stream, res)
+                     : sidx_host::stage_fd(c, fd, off, len, c->stream, res);
+  if (rc) return rc;
+  *d_out = c->d_in;
+  return 0;
+}
+
+// bytes of device memory (on the context's device) into host memory through its pinned staging
+int to_host(shockidx_ctx *c, const void *d_src, u64 bytes, void *dst, shockidx_result *res) {
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  return sidx_host::rows_to_host(c, (const sidx::u64 *)d_src, bytes, (uint8_t *)dst, c->stream, res);
 }
 
 void set_geometry(Slab &s, const uint8_t *d_win, u64 size, u64 lo, u64 hi, u64 wlo, u64 whi, int k) {
@@ -372,7 +385,7 @@ int multi_build(shockidx_multi *m, const void *data, int fd, u64 n, int kind, in
     Slab &s = S[k];
     memset(&s.r, 0, sizeof s.r);
     const uint8_t *d_win = nullptr;
-    if (int r = ctx_stage(m->ctx[k], data, fd, wlo[k], whi[k] - wlo[k], &d_win, &s.r)) return r;
+    if (int r = stage_window(m->ctx[k], data, fd, wlo[k], whi[k] - wlo[k], &d_win, &s.r)) return r;
     set_geometry(s, d_win, n, lo[k], hi[k], wlo[k], whi[k], k);
     const u64 bytes = hi[k] - lo[k];
     const u64 want = (kfmt == SHOCKIDX_FMT_LINE ? bytes / 16 : bytes / 32) + 4096;
@@ -406,12 +419,12 @@ int multi_build(shockidx_multi *m, const void *data, int fd, u64 n, int kind, in
   // 5. rows owned by each slab into the table at its first global record
   const u64 count = S[0].plan.count;
   const double td = now_ms();
-  uint64_t *out = alloc_rows(count * 16);
+  uint64_t *out = alloc_rows_out(count * 16);
   if (!out) return set_msg(res, SHOCKIDX_ENOMEM, "out of host memory");
   rc = par(w, [&](int k) -> int {
     const u64 own = rows_owned(S[k].plan, S[k].local_count, S[k].row_base);
     if (!own) return 0;
-    return ctx_to_host(m->ctx[k], S[k].d_rows, own * 16, out + 2 * S[k].plan.first_record, &S[k].r);
+    return to_host(m->ctx[k], S[k].d_rows, own * 16, out + 2 * S[k].plan.first_record, &S[k].r);
   });
   if (rc) {
     free(out);
@@ -603,7 +616,7 @@ int shockidx_multi_build_resident(shockidx_multi *m, uint64_t size, int kind, in
   if (rc) return rc;
   rc = check_seams(S.data(), w, size, kfmt, S[0].plan.count,
                    [&](int k, u64 i, u64 *o) -> int {
-                     return ctx_to_host(m->ctx[k], (const u64 *)d_rows[k] + 2 * i, 16, o, res);
+                     return to_host(m->ctx[k], (const u64 *)d_rows[k] + 2 * i, 16, o, res);
                    },
                    fetch, res);
   if (rc) return rc;

@@ -21,6 +21,7 @@
 
 #include "sidx_common.hpp"
 #include "sidx_subset.hpp"
+#include "sidx_launch.hpp"
 
 namespace sidx {
 
