@@ -187,3 +187,94 @@ def tiny(rng: random.Random) -> bytes:
         return b"".join(recs)
     return b"".join(rng.choice([b">", b"\n", b">a\n", b"AC", b" ", b"\r\n", b"\xc2\xa0", b"x>y"])
                     for _ in range(rng.randint(0, 14)))
+
+
+# ---- constructed FASTQ (tests/test_gpu_fastq_tiles.py): every byte placed on purpose --------------
+FQ_BAD = ("no_at", "empty_seq", "no_plus", "id_mismatch", "len_mismatch", "missing_id")  # of FASTQ_CORRUPTIONS
+
+
+def fq_id(nid: int, tag: int = 0) -> bytes:
+    """nid ID bytes without whitespace, '@' or '+', varying with tag."""
+    return bytes(ALNUM[(tag + 7 * i) % len(ALNUM)] for i in range(nid))
+
+
+def fq_lines(nid: int, nseq: int, *, eol=b"\n", plus_id=False, qual_at=False, tag=0, pad=b"", bad=None):
+    """The four lines (with their line ends) of one record: '@' + nid ID bytes, nseq bases, '+'
+    (with the ID repeated when plus_id), nseq quality bytes ('@' first when qual_at).  pad is
+    appended to the sequence line alone (Go trims it).  bad: one of FQ_BAD makes it invalid."""
+    rid = fq_id(nid, tag)
+    seq = (b"ACGTTGCA" * (nseq // 8 + 1))[:nseq]
+    qual = (b"@" if qual_at else b"I") + b"I" * (nseq - 1) if nseq else b""
+    plus = b"+" + rid if plus_id else b"+"
+    idl = b"@" + rid
+    if bad == "no_at":
+        idl = b"X" + rid
+    elif bad == "empty_seq":
+        seq = b""
+    elif bad == "no_plus":
+        plus = b"-" + plus[1:]
+    elif bad == "id_mismatch":
+        plus = b"+zz" + rid
+    elif bad == "len_mismatch":
+        qual += b"I"
+    elif bad == "missing_id":
+        idl = b"@"
+    elif bad is not None:
+        raise ValueError(bad)
+    return [idl + eol, seq + pad + eol, plus + eol, qual + eol]
+
+
+def fq_rec(nid: int, nseq: int, **kw) -> bytes:
+    return b"".join(fq_lines(nid, nseq, **kw))
+
+
+def fq_sized(nbytes: int, *, eol=b"\n", plus_id=False, nid=None, nseq=None, **kw) -> bytes:
+    """A valid record of exactly nbytes: the ID length given, or the sequence length given, or
+    neither (an ID of about 6 bytes); the other length follows (the ID one longer for parity)."""
+    fixed = 2 + 4 * len(eol)  # '@', '+' and four line ends
+    w = 2 if plus_id else 1
+    if nid is None:
+        if nseq is None:
+            nid = 6 if plus_id or (nbytes - fixed - 6) % 2 == 0 else 7
+            if w * nid + 2 + fixed > nbytes:
+                nid = 1 if plus_id or (nbytes - fixed - 1) % 2 == 0 else 2
+        else:
+            nid = (nbytes - fixed - 2 * nseq) // w
+    if nseq is None:
+        nseq = (nbytes - fixed - w * nid) // 2
+    rec = fq_rec(nid, nseq, eol=eol, plus_id=plus_id, **kw)
+    assert nid >= 1 and nseq >= 1 and len(rec) == nbytes, (nbytes, nid, nseq, len(rec))
+    return rec
+
+
+_FQ_FILL = [b"", 0]  # back-to-back 512-byte records, grown on demand
+
+
+def fq_fill(nbytes: int) -> bytes:
+    """Valid back-to-back records of exactly nbytes (0, or at least 9): fixed 512-byte records --
+    32 per 16 KiB tile, so filler tiles stay on the tile pass's fast path -- the last one longer
+    (its sequence, and its ID by one byte for parity) so the total is exact."""
+    if nbytes == 0:
+        return b""
+    assert nbytes >= 9, nbytes
+    k = nbytes // 512 - 1 if nbytes >= 1024 else 0
+    while _FQ_FILL[1] < k:
+        more = [fq_rec(6, 250, tag=_FQ_FILL[1] + i) for i in range(max(k - _FQ_FILL[1], 256))]
+        _FQ_FILL[0] += b"".join(more)
+        _FQ_FILL[1] += len(more)
+    out = _FQ_FILL[0][:512 * k] + fq_sized(nbytes - 512 * k, tag=k)
+    assert len(out) == nbytes
+    return out
+
+
+def fq_uniform(B: int, nbytes: int, extra: int = 0) -> bytes:
+    """Whole B-byte records (LF, bare plus line) up to at least nbytes, the first one extra bytes
+    longer so the rest are not tile-aligned."""
+    nid = 4 if B % 2 == 0 else 5
+    nseq = (B - 6 - nid) // 2
+    n = -(-nbytes // B)
+    pool = [fq_rec(nid, nseq, tag=t) for t in range(64)]
+    assert all(len(r) == B for r in pool)
+    first = fq_sized(B + extra, nid=nid + extra % 2, tag=1) if extra else pool[0]
+    reps = (n + 62) // 63
+    return first + (b"".join(pool[1:]) * reps)[:B * (n - 1)]

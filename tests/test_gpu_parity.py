@@ -120,8 +120,8 @@ def test_fastq_density_mix_gpu(gpu_ctx, oracle_lib):
     """Tiles of every record density back to back in one file: records of about 320 bytes (about
     50 per 16 KiB tile), of about 140 (past the 64 one wave certifies in one step), of about 14
     (more than the 256 starts a tile keeps: the tile goes to k_fixup whole) -- so the tile pass's
-    packed per-workgroup start arrays hold arrays of every length, and empty ones, at every
-    offset next to each other (round 5, SIDX_FQ_PACK)."""
+    per-tile start lines (64 entries each, the rest in the tile's overflow slot) are full, partly
+    filled and unused next to each other within one 16-tile store burst."""
     rng = random.Random(77)
     segs = []
     for i in range(24):
@@ -132,8 +132,8 @@ def test_fastq_density_mix_gpu(gpu_ctx, oracle_lib):
             segs.append(_fastq_seg(rng, rng.randint(100, 900), 50, 70, 4))
         else:
             segs.append(_fastq_seg(rng, rng.randint(500, 3000), 1, 3, 2))
-    # 40 copies: more tiles than the tile pass has workgroups, so workgroups append several
-    # arrays (the copies' offsets relative to the tiles all differ: 952,820 bytes each)
+    # 40 copies: every segment at 40 offsets relative to the tiles, bursts and batches (the
+    # copies' offsets all differ: 952,820 bytes each)
     data = b"".join(segs) * 40
     for mode in ("fastq", "auto"):
         _check(gpu_ctx, oracle_lib, data, mode)
