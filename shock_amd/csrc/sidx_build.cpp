@@ -119,8 +119,9 @@ int ensure_dev(shockidx_ctx *c, void **p, u64 *cap, u64 need, size_t elem, shock
 // device bytes held by the context's grow-only caches (input staging, rows, tile status,
 // scan and subset workspaces)
 u64 workspace_bytes(const shockidx_ctx *c) {
+  // (13 undercounts the per-tile words: ensure_tiles holds STATUS_ARRAYS + 4 detail + 4 fix = 15; to be fixed)
   return c->d_in_cap + 16 * c->d_rows_cap + 13 * 8 * c->tiles_cap + c->d_sub_cap +
-         4 * (c->fqstage_cap + c->fqtiles_cap) + 2 * c->fqlines_cap + c->cra_cap + c->crb_cap + 2 * c->slot_cap;
+         4 * (c->tile_stage_cap + c->tile_words_cap) + 2 * c->fqlines_cap + c->cra_cap + c->crb_cap + 2 * c->slot_cap;
 }
 
 // free the large caches (they regrow on demand); the tile status words go only with keep = 0
@@ -135,8 +136,8 @@ void trim_workspace(shockidx_ctx *c, u64 keep) {
   drop((void *&)c->d_in, c->d_in_cap);
   drop((void *&)c->d_rows, c->d_rows_cap);
   drop((void *&)c->d_sub, c->d_sub_cap);
-  drop((void *&)c->d_fqstage, c->fqstage_cap);
-  drop((void *&)c->d_fqtiles, c->fqtiles_cap);
+  drop((void *&)c->d_tile_stage, c->tile_stage_cap);
+  drop((void *&)c->d_tile_words, c->tile_words_cap);
   drop((void *&)c->d_fqlines, c->fqlines_cap);
   c->last_spans = false;
   drop((void *&)c->d_cra, c->cra_cap);
@@ -157,10 +158,10 @@ void trim_workspace(shockidx_ctx *c, u64 keep) {
 
 // test hook: every status word published (INC) with the next build's epoch and payload 0, on
 // the build stream -- the stale look-back words a recycled allocation could hold
-static hipError_t poison_status(shockidx_ctx *c, u64 words) {
+static hipError_t poison_status(shockidx_ctx *c, u64 tiles_cap) {
   const u64 w = FLAG_INC | ((u64)((c->epoch + 1) & EPOCH_MASK) << EPOCH_SHIFT);
-  std::vector<u64> h(words, w);
-  hipError_t e = hipMemcpyAsync(c->d_status, h.data(), words * sizeof(u64), hipMemcpyHostToDevice, c->stream);
+  std::vector<u64> h(STATUS_ARRAYS * tiles_cap, w);
+  hipError_t e = hipMemcpyAsync(c->d_status, h.data(), h.size() * sizeof(u64), hipMemcpyHostToDevice, c->stream);
   return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
 }
 
@@ -175,17 +176,16 @@ static int ensure_tiles(shockidx_ctx *c, u64 ntiles, shockidx_result *res) {
   c->d_status = nullptr;
   c->d_detail = nullptr;
   u64 want = ntiles + ntiles / 8 + 64;
-  // status words: slab aggregate (last tile's word) | line: last '\n' per tile | its max scan |
-  // scan look-back words (two scans) | tile aggregates | their exclusive prefixes
-  HIPCHK(dev_malloc((void **)&c->d_status, 7 * want * sizeof(u64), ws_contig(1)), "hipMalloc(status)");
+  // the status block: STATUS_ARRAYS words per tile (StatusArray, sidx_host.hpp)
+  HIPCHK(dev_malloc((void **)&c->d_status, STATUS_ARRAYS * want * sizeof(u64), ws_contig(1)), "hipMalloc(status)");
   // detail slots: one per tile (+1) and one per k_fixup queue item (the FASTA tile pass)
   HIPCHK(hipMalloc((void **)&c->d_detail, 4 * want * sizeof(u64)), "hipMalloc(detail)");
   HIPCHK(hipMalloc((void **)&c->d_fix, 4 * want * sizeof(u64)), "hipMalloc(fix)");
   // on the build stream and waited for: a null-stream memset is not ordered with the
   // non-blocking context stream, and a reused allocation's old look-back words could be read
-  if (c->inject & 1) HIPCHK(poison_status(c, 7 * want), "poison");
-  HIPCHK(hipMemsetAsync(c->d_status, 0, 7 * want * sizeof(u64), c->stream), "hipMemset(status)");
-  if (c->inject & 2) HIPCHK(poison_status(c, 7 * want), "poison");
+  if (c->inject & 1) HIPCHK(poison_status(c, want), "poison");
+  HIPCHK(hipMemsetAsync(c->d_status, 0, STATUS_ARRAYS * want * sizeof(u64), c->stream), "hipMemset(status)");
+  if (c->inject & 2) HIPCHK(poison_status(c, want), "poison");
   HIPCHK(hipStreamSynchronize(c->stream), "hipMemset(status) sync");
   c->tiles_cap = want;
   return 0;
@@ -257,6 +257,25 @@ static std::mutex &device_mutex(int device) {
   return mu[device & 63];
 }
 
+// SHOCKIDX_{FA,LINE,SAM}_MODE=two (or 0): two-pass instead of the tile pass; read per build, for in-process A/B
+static bool forced_two_pass(const char *envname) {
+  const char *e = getenv(envname);
+  return e && (!strcmp(e, "two") || !strcmp(e, "0"));
+}
+
+// The build path of one slab.  Tile passes (one read of the input): FASTQ, FASTA (detail slots of
+// tiles + queue items within the key) and line, single builds and slabs alike; SAM single builds
+// (slabs keep their halo handling).  Otherwise the two-pass build (k_tile_agg + scan + k_index1).
+static TilePass choose_pass(const shockidx_ctx *c, int kfmt, u64 n, const SlabGeom *geom, bool general) {
+  if (general || !c->d_fix) return TP_TWO_PASS;  // (no k_fixup queue: k_index1 for every format)
+  if (kfmt == F_FASTQ) return TP_FQ;
+  const bool fa_key_fits = 2 * c->tiles_cap < (1ull << KEY_TILE_BITS);
+  if (kfmt == F_FASTA && (!geom || n > 0) && !forced_two_pass("SHOCKIDX_FA_MODE") && fa_key_fits) return TP_FA;
+  if (kfmt == F_LINE && n > 0 && !forced_two_pass("SHOCKIDX_LINE_MODE")) return TP_LINE;
+  if (kfmt == F_SAM && n > 0 && !geom && !forced_two_pass("SHOCKIDX_SAM_MODE")) return TP_SAM;
+  return TP_TWO_PASS;
+}
+
 // One device-resident index pass.  Fills *dr (host copy of the device result).
 int run_index(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kfmt, u64 *d_rows, u64 row_cap,
               hipStream_t s, DevResult *dr, shockidx_result *res, const SlabGeom *geom, bool general,
@@ -264,22 +283,13 @@ int run_index(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kfmt, u64 *d_ro
   const u64 ntiles = n ? (n + TILE - 1) / TILE : 1;
   if (ntiles >= (1ull << KEY_TILE_BITS)) return set_msg(res, SHOCKIDX_EINVAL, "input too large for one slab");
   if (int rc = ensure_tiles(c, ntiles, res)) return rc;
-  const bool fq_tiles0 = !general && kfmt == F_FASTQ;
-  const bool fa_tiles0 = !general && kfmt == F_FASTA && (!geom || n > 0) && sidx_fa_tiles() &&
-                         2 * c->tiles_cap < (1ull << KEY_TILE_BITS);
-  const bool ln_tiles0 = !general && kfmt == F_LINE && n > 0 && sidx_line_tiles();
-  // SAM: single-slab builds (slabs keep the two-pass build and its halo handling)
-  const bool sm_tiles0 = !general && kfmt == F_SAM && n > 0 && !geom && sidx_sam_tiles();
-  if (fq_tiles0 || fa_tiles0 || ln_tiles0 || sm_tiles0) {  // provisional rows and per-tile results
-    // (FASTQ: a 128-byte line + an overflow slot per tile, sidx_kernels.hip fq_start; 1 KiB per tile here)
-    if (int rc = ensure_dev(c, (void **)&c->d_fqstage, &c->fqstage_cap,
-                            (ln_tiles0 || sm_tiles0) ? ntiles * (TILE / 32) : (ntiles + c->tiles_grid + 16) * (TILE / 64), 4,
-                            res, ws_contig(2)))
-      return rc;
-    if (int rc = ensure_dev(c, (void **)&c->d_fqtiles, &c->fqtiles_cap, ntiles * FQ_TILE_WORDS, 4, res)) return rc;
-  }
-  if (fq_tiles0 && c->want_spans) {
-    if (int rc = ensure_dev(c, (void **)&c->d_fqlines, &c->fqlines_cap, ntiles * 3 * (TILE / 64), 2, res)) return rc;
+  const TilePass pass = choose_pass(c, kfmt, n, geom, general);
+  if (pass != TP_TWO_PASS) {  // the tile pass's staged positions and per-tile results
+    const u64 words = sidx_tile_stage_words(pass, ntiles, c->tiles_grid);
+    if (int rc = ensure_dev(c, (void **)&c->d_tile_stage, &c->tile_stage_cap, words, 4, res, ws_contig(2))) return rc;
+    if (int rc = ensure_dev(c, (void **)&c->d_tile_words, &c->tile_words_cap, ntiles * FQ_TILE_WORDS, 4, res)) return rc;
+    if (pass == TP_FQ && c->want_spans)
+      if (int rc = ensure_dev(c, (void **)&c->d_fqlines, &c->fqlines_cap, ntiles * 3 * (TILE / 64), 2, res)) return rc;
   }
   if (getenv("SHOCKIDX_TIMING") && !c->d_timing) {
     HIPCHK(hipMalloc((void **)&c->d_timing, 9 * 8 * 65536), "hipMalloc(timing)");
@@ -295,7 +305,7 @@ int run_index(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kfmt, u64 *d_ro
   // next epoch (taken only once every allocation above succeeded); when the 14-bit epoch wraps,
   // clear the status array so no stale word can carry the current epoch
   if (++c->epoch > EPOCH_MASK) {
-    HIPCHK(hipMemsetAsync(c->d_status, 0, 7 * c->tiles_cap * sizeof(u64), s), "status clear");
+    HIPCHK(hipMemsetAsync(c->d_status, 0, STATUS_ARRAYS * c->tiles_cap * sizeof(u64), s), "status clear");
     c->epoch = 2;  // keep the slot parity alternating across the wrap (EPOCH_MASK is odd)
   }
   c->slots_dirty = true;  // until this build's finalize has run (the sync below)
@@ -312,13 +322,13 @@ int run_index(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kfmt, u64 *d_ro
   p.summary = geom ? (u64 *)geom->d_summary : nullptr;
   p.row_cap = row_cap;
   p.rows = d_rows;
-  p.status = c->d_status;
-  p.pcnt = c->d_status + c->tiles_cap;
-  p.ppre = c->d_status + 2 * c->tiles_cap;
-  p.scan_look[0] = c->d_status + 3 * c->tiles_cap;
-  p.scan_look[1] = c->d_status + 4 * c->tiles_cap;
-  p.fq_agg = c->d_status + 5 * c->tiles_cap;
-  p.tile_excl = c->d_status + 6 * c->tiles_cap;
+  auto status_array = [c](StatusArray a) { return c->d_status + (u64)a * c->tiles_cap; };
+  p.status = status_array(SA_STATUS);
+  p.pcnt = status_array(SA_PCNT);
+  p.ppre = status_array(SA_PPRE);
+  for (int i = 0; i < 2; ++i) p.scan_look[i] = status_array((StatusArray)(SA_LOOK0 + i));
+  p.tile_agg = status_array(SA_TILE_AGG);
+  p.tile_excl = status_array(SA_TILE_EXCL);
   p.pgrid = c->tiles_grid < ntiles ? c->tiles_grid : (u32)ntiles;
   p.fix = general ? nullptr : c->d_fix;  // null: the two-pass build (k_index1) for every format
   p.fixcap = (u32)c->tiles_cap;
@@ -334,26 +344,19 @@ int run_index(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kfmt, u64 *d_ro
   p.eof = geom ? geom->eof : 1;
   p.file_start = geom ? geom->file_start : 1;
   p.gate = gate;
-  p.gate_fmt = kfmt;
+  p.gate_fmt = kfmt;  // (also the format the two-pass launch instantiates)
   if (const char *dbg = getenv("SHOCKIDX_DEBUG")) p.debug = (u32)atoi(dbg);  // SIDX_DIAG variant ablations
   if (getenv("SHOCKIDX_TIMING")) {  // diagnostic phase timing: per-workgroup cycle sums
     HIPCHK(hipMemsetAsync(c->d_timing, 0, 9 * 8 * 65536, s), "timing clear");
     p.timing = c->d_timing;
   }
   DevResult *d_res = (DevResult *)(c->d_small + SMALL_RESULT);
-  // tile passes (one read of the input): FASTQ, FASTA (detail slots of tiles + queue items
-  // within the key) and line, single builds and slabs alike; SAM single builds.  Otherwise (SAM
-  // slabs, the general re-run) the two-pass build (k_tile_agg + scan + k_index1).
-  const bool tiles = !general && p.fix;
-  const bool fq_tiles = tiles && fq_tiles0;
-  const bool fa_tiles = tiles && fa_tiles0;
-  const bool ln_tiles = tiles && ln_tiles0;
-  const bool sm_tiles = tiles && sm_tiles0;
-  if (fq_tiles || fa_tiles || ln_tiles || sm_tiles) {
-    p.fq_stage = c->d_fqstage;
-    p.fq_tiles = c->d_fqtiles;
+  const bool tile_pass = pass != TP_TWO_PASS;
+  if (tile_pass) {
+    p.tile_stage = c->d_tile_stage;
+    p.tile_words = c->d_tile_words;
   }
-  p.fq_lines = (fq_tiles && c->want_spans) ? c->d_fqlines : nullptr;
+  p.fq_lines = (pass == TP_FQ && c->want_spans) ? c->d_fqlines : nullptr;
   c->last_spans = false;
   // One build's device work at a time per GPU: each build alone saturates HBM, so builds
   // from different contexts (concurrent goroutines, §8(b) "Threading") run back to back
@@ -362,15 +365,12 @@ int run_index(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kfmt, u64 *d_ro
   // the build's device time runs from its first kernel's start to the end of its last one: a
   // tile pass records its start (and end) in its own dispatch packet (hipExtLaunchKernel), so
   // its start event is ev0; the two-pass build brackets its kernels with stream events
-  const bool tile_pass = fq_tiles || fa_tiles || ln_tiles || sm_tiles;
   hipEvent_t k0 = tile_pass ? c->ev0 : c->ek0;
   if (!tile_pass) HIPCHK(hipEventRecord(c->ev0, s), "event");
-  if (fq_tiles) HIPCHK(sidx_launch_fq_tiles(&p, d_res, s, k0, c->ek1), "tile pass launch");
-  else if (fa_tiles) HIPCHK(sidx_launch_fa_tiles(&p, d_res, s, k0, c->ek1), "FASTA tile pass launch");
-  else if (ln_tiles) HIPCHK(sidx_launch_line_tiles(&p, d_res, s, k0, c->ek1), "line tile pass launch");
-  else if (sm_tiles) HIPCHK(sidx_launch_sam_tiles(&p, d_res, s, k0, c->ek1), "SAM tile pass launch");
-  else HIPCHK(sidx_launch_index(kfmt, &p, d_res, s, k0, c->ek1), "index launch");
-  if (res) res->path = (fq_tiles || fa_tiles || ln_tiles || sm_tiles) ? 1u : 2u;
+  static const char *const what[] = {"index launch", "tile pass launch", "FASTA tile pass launch",
+                                     "line tile pass launch", "SAM tile pass launch"};  // by TilePass
+  HIPCHK(sidx_launch_tiles(pass, &p, d_res, s, k0, c->ek1), what[pass]);
+  if (res) res->path = tile_pass ? 1u : 2u;
   HIPCHK(hipEventRecord(c->ev1, s), "event");
   // SHOCKIDX_VERIFY (the GPU test suite): the whole table's contiguity, after the timed kernels
   if (d_rows && verify_rows()) HIPCHK(sidx_launch_verify_rows(d_rows, p.row_base, row_cap, d_res, s), "verify launch");

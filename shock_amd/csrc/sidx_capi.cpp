@@ -175,8 +175,8 @@ void shockidx_ctx_destroy(shockidx_ctx *c) {
   if (c->h_res) (void)hipHostFree(c->h_res);
   if (c->h_det) (void)hipHostFree(c->h_det);
   (void)hipFree(c->d_sub);
-  (void)hipFree(c->d_fqstage);
-  (void)hipFree(c->d_fqtiles);
+  (void)hipFree(c->d_tile_stage);
+  (void)hipFree(c->d_tile_words);
   (void)hipFree(c->d_fqlines);
   (void)hipFree(c->d_cra);
   (void)hipFree(c->d_crb);

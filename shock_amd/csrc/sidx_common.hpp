@@ -78,6 +78,10 @@ constexpr int KEY_REC_SHIFT = 4 + KEY_TILE_BITS;
 constexpr u64 KEY_NONE = ~0ull;
 constexpr int NCOUNTERS = 8;  // u32 counters per build slot
 
+// How one slab is built: the two-pass build (k_tile_agg + scan + k_index1, every format) or one
+// of the tile passes that read the input once.
+enum TilePass : int { TP_TWO_PASS = 0, TP_FQ, TP_FA, TP_LINE, TP_SAM };
+
 // Kernel parameters for one slab.
 struct SlabParams {
   const uint8_t *data;   // slab bytes (16-byte aligned), readable up to data[end)
@@ -112,21 +116,22 @@ struct SlabParams {
   u64 *scan_look[2];
   u32 pgrid;             // persistent grid of the tile passes
   u32 seq;               // multi-GPU: the caller's build tag, stamped into the slab summary
-  u64 *fix;              // k_fixup queue (32-byte items); counters[2] = items, counters[3] = overflow
+  u64 *fix;              // k_fixup queue (FixRec items, 24 bytes); counters[2] = items, counters[3] = overflow
   u32 fixcap;
   // exclusive monoid prefix of every tile's aggregate (k_scan_excl): k_index1's incoming
   // states, the tile passes' record / row bases
   const u64 *tile_excl;
-  // per-tile monoid aggregates (two-pass and tile passes); FASTQ tile pass provisional rows
-  // (RCAP u32 per tile: start | length << 16) and per-tile results (FQ_TILE_WORDS u32)
-  u64 *fq_agg;
-  u32 *fq_stage;
-  u32 *fq_tiles;
+  // per-tile words of every build path: the monoid aggregate (two-pass build) or the tile pass's
+  // packed word that holds it; the tile passes' staged positions (tile_stage_words() u32) and
+  // per-tile results (FQ_TILE_WORDS u32)
+  u64 *tile_agg;
+  u32 *tile_stage;
+  u32 *tile_words;
   // format speculation (single builds with auto-detection): every kernel of the pipeline exits
   // at once unless k_detect's result *gate equals gate_fmt; k_finalize then reports flag 16 and
   // the detected format, and the host re-runs with it.  Null: no gate.
   const int *gate;
-  int gate_fmt;
+  int gate_fmt;          // the format this build indexes (F_*), set for every build
   u32 inject;            // test hooks (shockidx_debug_inject): bit0 finalize reports one record short
   // download filters over FASTQ (k_fq_tiles<true>): per record its three inner line ends
   // (3 u16 per record, RCAP records per tile; sidx_filter.hip's spans come from them)

@@ -1,5 +1,6 @@
 // sidx_device.hpp -- device-side building blocks for the gfx950 record indexer:
-// SWAR byte classification, the per-format look-back monoids, ordered wave scans,
+// SWAR byte classification, the per-format look-back monoids, ordered wave scans (monoid and
+// DPP), the pieces the tile passes share (first-bad key, FASTQ tile word, k_fixup item),
 // Go bytes.TrimSpace / utf8 restated for the device, and the two byte accessors
 // (lane: LDS tile + masks; wave: cooperative global-memory scan).
 #pragma once
@@ -210,6 +211,121 @@ template <class M>
 __device__ __forceinline__ u64 wave_total_in_order(u64 v, int lane) {
   const u64 inc = wave_incl_scan<M>(v, lane);
   return __shfl(inc, 63, 64);
+}
+
+// Inclusive add-scan over a wave in DPP steps (row shifts 1/2/4/8, then the two row
+// broadcasts): no LDS round trips, unlike __shfl_up (ds_bpermute).
+__device__ __forceinline__ u32 wave_scan_add(u32 v) {
+  v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);  // row_shr:1
+  v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);  // row_shr:2
+  v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);  // row_shr:4
+  v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);  // row_shr:8
+  v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15
+  v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast:31
+  return v;
+}
+
+__device__ __forceinline__ u32 umax(u32 a, u32 b) { return a > b ? a : b; }
+
+// lanes below this one with their bit set in b
+__device__ __forceinline__ u32 mbcnt64(u64 b) {
+  return __builtin_amdgcn_mbcnt_hi((u32)(b >> 32), __builtin_amdgcn_mbcnt_lo((u32)b, 0u));
+}
+// inclusive wave scan of small per-lane counts: two ballots and their lane-prefix counts when
+// every count is below 4 (a 64-byte word holds at most three '\n' unless lines are under ~21
+// bytes), else the DPP scan -- 7 VALU instead of 12
+__device__ __forceinline__ u32 wave_scan_add_small(u32 c) {
+  if (__ballot(c > 3u) == 0) {
+    const u64 b1 = __ballot(c & 1u), b2 = __ballot(c & 2u);
+    return mbcnt64(b1) + 2u * mbcnt64(b2) + c;
+  }
+  return wave_scan_add(c);
+}
+
+// wave-inclusive scans over DPP row shifts / broadcasts (no LDS round trips; 0 fills the lanes a
+// shift leaves without a source, as in wave_scan_add: OP's identity must be 0)
+#define SIDX_DPP_SCAN(v, OP)                                                                   \
+  do {                                                                                         \
+    v = OP((u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false), v);            \
+    v = OP((u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false), v);            \
+    v = OP((u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false), v);            \
+    v = OP((u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false), v);            \
+    v = OP((u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false), v);            \
+    v = OP((u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false), v);            \
+  } while (0)
+__device__ __forceinline__ u32 wave_scan_max(u32 v) { SIDX_DPP_SCAN(v, umax); return v; }
+
+// ------------------------------------------------------------------------------------
+// Pieces shared by the tile passes and their placement / fix-up kernels
+// ------------------------------------------------------------------------------------
+// First-bad key (sidx_common.hpp): record index | tile or detail slot | status; the slab's
+// result is the minimum over every key reported.
+__device__ __forceinline__ u64 bad_key(u64 rec, u32 slot, u32 st) {
+  return (rec << KEY_REC_SHIFT) | ((u64)(slot & ((1u << KEY_TILE_BITS) - 1)) << 4) | st;
+}
+
+// A persistent workgroup's first tile (then t += G): with a grid that is a multiple of the 8
+// XCDs, workgroups are dealt round-robin to the XCDs, so XCD x takes the tiles G / 8 * x ..
+// and neighbouring tiles share an L2.
+__device__ __forceinline__ u64 first_tile(u32 bid, u64 G) {
+  u64 t = bid;
+  if ((G & 7) == 0) t = (bid & 7) * (G >> 3) + (bid >> 3);
+  return t;
+}
+
+// The LDS-DMA's range check is per dword: a slab's partial last dword came back as zeros.  In the
+// thread whose 64-byte mask word holds them (no other thread, no other tile), f(byte, bit) for
+// each of those bytes, read from global memory; tlen = the tile's owned bytes.
+template <class F>
+__device__ __forceinline__ void tail_bytes(const SlabParams &p, u64 tlo, u32 tlen, int tid, F f) {
+  if (tlen < (u32)TILE && (tlen & 3u) && (u32)tid == ((tlen - 1) >> 6))
+    for (u32 i = tlen & ~3u; i < tlen; ++i) f(p.data[tlo + i], i - (u32)tid * 64);
+}
+
+// k_fixup / k_fa_fixup work item (SlabParams::fix): one record, or one whole tile (start == ~0)
+constexpr u32 FIX_HALO = 0x80000000u;  // FixRec::tile flag (FASTA / line slabs): a record closed in the halo
+struct FixRec {
+  u64 start;             // file-relative start of the record (slab offset)
+  u64 g;                 // its global record number; for a tile: the tile's rank j0
+  u32 tile;
+  u32 pad;
+};
+static_assert(sizeof(FixRec) == 24, "the queue is strided by FixRec (push_fix)");
+
+// The FASTQ tile word (tile_agg[t]).  Every byte the tile pass writes is expensive next to the
+// bytes it streams in, so a tile writes this one u64; the scan folds its newline count.
+// (nrec: 9 bits -- a tile keeps at most RCAP records' starts, more makes it slow and nrec unused)
+constexpr int RCAP = TILE / 64;  // records per tile kept in the provisional row slot
+constexpr u32 GUESS_NONE = 4;    // no record phase could be read off the tile
+constexpr u32 FQW_T = 0, FQW_GI = 16, FQW_NREC = 19, FQW_SLOW = 28, FQW_NDEF = 29;
+constexpr u32 FQW_NRECM = 0x1FF;
+constexpr u64 FQW_TMASK = 0xFFFF;  // the newline count: what the scan folds
+__device__ __forceinline__ u64 fq_word(u32 T, u32 gi0, u32 nrec, bool slow, u32 ndefer) {
+  return ((u64)T << FQW_T) | ((u64)(gi0 & 7u) << FQW_GI) | ((u64)(nrec < FQW_NRECM ? nrec : FQW_NRECM) << FQW_NREC) |
+         ((u64)(slow || nrec > (u32)RCAP) << FQW_SLOW) | ((u64)ndefer << FQW_NDEF);
+}
+// What the kernels after the scan read off a tile's word and its true newline rank j0.
+struct FqTileWord {
+  u32 nrec, nd;  // records whose starts the tile kept; of which deferred to k_fixup
+  bool redo;     // slow, or the phase read off the tile was wrong: the whole tile goes to k_fixup
+  u64 gbase;     // global number of the tile's local record 0
+  u64 j0;        // rank of the tile's first '\n'
+};
+__device__ __forceinline__ FqTileWord fq_unpack(const SlabParams &p, u64 t) {
+  const u64 w = p.tile_agg[t];
+  const u32 Te = (u32)(w >> FQW_T) & 0xFFFFu;
+  const u32 gi = (u32)(w >> FQW_GI) & 7u;
+  const u32 i0 = gi == 7u ? GUESS_NONE : gi;
+  FqTileWord f;
+  f.nrec = (u32)(w >> FQW_NREC) & FQW_NRECM;
+  f.nd = (u32)(w >> FQW_NDEF) & 0x1Fu;
+  f.j0 = p.state_in + p.tile_excl[t];
+  const u32 ti0 = (u32)((3 - (f.j0 & 3)) & 3);
+  const u32 ngt = ti0 < Te ? (Te - ti0 + 3) / 4 : 0;
+  const u32 ngg = i0 < Te ? (Te - i0 + 3) / 4 : 0;
+  f.redo = ((w >> FQW_SLOW) & 1u) || (i0 != ti0 && (ngt | ngg) != 0);
+  f.gbase = ((f.j0 + ti0 + 1) >> 2) - ((p.file_start && t == 0) ? 1u : 0u);
+  return f;
 }
 
 // ------------------------------------------------------------------------------------

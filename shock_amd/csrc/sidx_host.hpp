@@ -25,6 +25,10 @@ constexpr int NSTAGE = 2;
 // c->d_small: badkey slots at +0/+8, counter slots at +64/+80
 constexpr size_t SMALL_BADKEY = 0, SMALL_COUNTERS = 64, SMALL_RESULT = 128, SMALL_DETECT = 320, SMALL_CHUNK = 384,
                  SMALL_SLABSUM = 448, SMALL_BYTES = 512;
+// c->d_status: sub-arrays of tiles_cap u64 words each, in this order.  SA_STATUS's word
+// ntiles - 1 is the slab aggregate k_finalize reads; the rest are SlabParams' pcnt, ppre,
+// scan_look[0..1], tile_agg and tile_excl.
+enum StatusArray : int { SA_STATUS, SA_PCNT, SA_PPRE, SA_LOOK0, SA_LOOK1, SA_TILE_AGG, SA_TILE_EXCL, STATUS_ARRAYS };
 
 inline double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -66,9 +70,9 @@ struct shockidx_ctx {
   u64 d_in_cap = 0;
   u64 *d_rows = nullptr;
   u64 d_rows_cap = 0;  // rows
-  u64 *d_status = nullptr;
+  u64 *d_status = nullptr;  // STATUS_ARRAYS sub-arrays of tiles_cap words each (StatusArray)
   u64 *d_detail = nullptr;
-  u64 *d_fix = nullptr;  // k_fixup queue (FixRec, 32 bytes each), tiles_cap items
+  u64 *d_fix = nullptr;  // k_fixup queue (FixRec, 24 bytes each), tiles_cap items
   u64 tiles_cap = 0;
   uint8_t *d_small = nullptr;  // badkey[2] | counters[2][NCOUNTERS] | result | detect
   u32 epoch = 0;               // build epoch for the look-back words (1..EPOCH_MASK)
@@ -85,10 +89,10 @@ struct shockidx_ctx {
   u64 ws_cap = 0;                  // SHOCKIDX_WORKSPACE_CAP: trim the caches above this after a call
   u64 dev_cap = 0;                 // device bytes a build may hold (0: what the device has free;
                                    //   shockidx_ctx_set_dev_cap / SHOCKIDX_DEV_CAP)
-  u32 *d_fqstage = nullptr;        // FASTQ tile pass: provisional rows (TILE / 64 per tile)
-  u64 fqstage_cap = 0;             //   (u32 entries)
-  u32 *d_fqtiles = nullptr;        //   per-tile results (FQ_TILE_WORDS per tile)
-  u64 fqtiles_cap = 0;
+  u32 *d_tile_stage = nullptr;     // tile passes: staged positions (tile_stage_words() u32 entries)
+  u64 tile_stage_cap = 0;
+  u32 *d_tile_words = nullptr;     //   per-tile results (FQ_TILE_WORDS per tile)
+  u64 tile_words_cap = 0;
   uint8_t *d_cra = nullptr;        // speculative chunkrecord: FASTQ record table / FASTA tile counts
   u64 cra_cap = 0;                 //   (bytes)
   uint8_t *d_crb = nullptr;        //   node positions, jump tables, path, results (bytes)

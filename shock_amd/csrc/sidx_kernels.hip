@@ -1,14 +1,14 @@
-// sidx_kernels.hip -- gfx950 kernels of the MI355X record indexer.
+// sidx_kernels.hip -- gfx950 kernels of the MI355X record indexer: every kernel of an index
+// build (format detection, the slab exchange and the table check are in sidx_control.hip).
 //
-//   k_detect       format detection (multi.go:43-62), one workgroup, <= 32 KiB inspected
 //   k_fq_tiles     FASTQ tile pass: LDS-DMA staged 16 KiB tiles, '\n' masks, the record phase
 //                  read off the tile, records certified from LDS into a provisional row table
 //   k_fa_tiles     FASTA tile pass (the FastaMonoid boundaries, pieces validated from LDS)
-//   k_line_tiles   line tile pass ('\n' positions per tile)
+//   k_line_tiles   line tile pass ('\n' positions per tile); k_sam_tiles the SAM one (terminator lines)
 //   k_scan_excl<M> device-wide exclusive scan of the per-tile aggregates (decoupled look-back)
 //   k_*_place      final 16-byte rows at their global record numbers; k_fixup / k_fa_fixup
 //                  re-validate from global memory what a tile could not settle
-//   k_tile_agg<F> + k_index1<F>  the two-pass build (SAM, FASTA / line slabs, re-runs)
+//   k_tile_agg<F> + k_index1<F>  the two-pass build (SAM slabs, re-runs)
 //   k_finalize   folds the slab's terminal state + first-bad key into a DevResult
 //
 // Reference semantics restated (paths relative to /root/reference/shock-server/):
@@ -24,8 +24,6 @@
 #include "sidx_common.hpp"
 #include "sidx_device.hpp"
 #include "sidx_launch.hpp"
-#include <stdlib.h>
-#include <string.h>
 
 namespace sidx {
 
@@ -251,7 +249,7 @@ __device__ __forceinline__ void put_row(const SlabParams &p, u64 k, u64 s, u64 l
 }
 
 __device__ __forceinline__ void note_bad(Bad &b, u64 k, u32 tile, u32 st, u64 pos, u64 len) {
-  const u64 key = (k << KEY_REC_SHIFT) | ((u64)(tile & ((1u << KEY_TILE_BITS) - 1)) << 4) | st;
+  const u64 key = bad_key(k, tile, st);
   if (key < b.key) { b.key = key; b.pos = pos; b.len = len; }
 }
 
@@ -826,19 +824,6 @@ __global__ __launch_bounds__(NTHREADS) void k_index1(const SlabParams p) {
 // Tile-pass building blocks (k_fq_tiles / k_fa_tiles / k_line_tiles): result encodings,
 // the k_fixup queue, the LDS certifiers and the device-scope atomics they use.
 // ====================================================================================
-constexpr int RCAP = TILE / 64;  // records per tile kept in the provisional row slot
-constexpr u32 GUESS_NONE = 4;
-
-
-constexpr u32 FIX_HALO = 0x80000000u;  // FixRec::tile flag (FASTA / line slabs): a record closed in the halo
-struct FixRec {          // k_fixup work item: one record, or one whole tile (start == ~0)
-  u64 start;             // file-relative start of the record (slab offset)
-  u64 g;                 // its global record number; for a tile: the tile's rank j0
-  u32 tile;
-  u32 pad;
-};
-
-
 // ASCII bytes.TrimSpace bounds of r[lo, hi); false if a byte >= 0x80 decides (Unicode path)
 __device__ __forceinline__ bool trim_ascii(const uint8_t *r, u32 lo, u32 hi, u32 &tl, u32 &th) {
   while (lo < hi) {
@@ -857,36 +842,6 @@ __device__ __forceinline__ bool trim_ascii(const uint8_t *r, u32 lo, u32 hi, u32
   return true;
 }
 
-// Inclusive add-scan over a wave in DPP steps (row shifts 1/2/4/8, then the two row
-// broadcasts): no LDS round trips, unlike __shfl_up (ds_bpermute).
-__device__ __forceinline__ u32 wave_scan_add(u32 v) {
-  v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);  // row_shr:1
-  v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);  // row_shr:2
-  v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);  // row_shr:4
-  v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);  // row_shr:8
-  v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15
-  v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast:31
-  return v;
-}
-
-
-__device__ __forceinline__ u32 umax(u32 a, u32 b) { return a > b ? a : b; }
-
-// lanes below this one with their bit set in b
-__device__ __forceinline__ u32 mbcnt64(u64 b) {
-  return __builtin_amdgcn_mbcnt_hi((u32)(b >> 32), __builtin_amdgcn_mbcnt_lo((u32)b, 0u));
-}
-// inclusive wave scan of small per-lane counts: two ballots and their lane-prefix counts when
-// every count is below 4 (a 64-byte word holds at most three '\n' unless lines are under ~21
-// bytes), else the DPP scan -- 7 VALU instead of 12
-__device__ __forceinline__ u32 wave_scan_add_small(u32 c) {
-  if (__ballot(c > 3u) == 0) {
-    const u64 b1 = __ballot(c & 1u), b2 = __ballot(c & 2u);
-    return mbcnt64(b1) + 2u * mbcnt64(b2) + c;
-  }
-  return wave_scan_add(c);
-}
-
 // FastaMonoid::combine on 32-bit aggregates (a wave's count of '>' fits 13 bits)
 __device__ __forceinline__ u32 fa_comb32(u32 a, u32 b) {
   const u32 af = a & 3u, bf = b & 3u;
@@ -896,19 +851,7 @@ __device__ __forceinline__ u32 fa_comb32(u32 a, u32 b) {
   const u32 f = bf == 0u ? af : bf;
   return (cnt << 3) | (d << 2) | f;
 }
-// wave-inclusive scans over DPP row shifts / broadcasts (no LDS round trips; identity 0 fills
-// the lanes a shift leaves without a source, as in wave_scan_add)
-#define SIDX_DPP_SCAN(v, OP)                                                                   \
-  do {                                                                                         \
-    v = OP((u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false), v);            \
-    v = OP((u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false), v);            \
-    v = OP((u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false), v);            \
-    v = OP((u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false), v);            \
-    v = OP((u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false), v);            \
-    v = OP((u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false), v);            \
-  } while (0)
 __device__ __forceinline__ u32 wave_scan_fa32(u32 v) { SIDX_DPP_SCAN(v, fa_comb32); return v; }
-__device__ __forceinline__ u32 wave_scan_max(u32 v) { SIDX_DPP_SCAN(v, umax); return v; }
 
 // bytes that differ between raw[a, a+4) and raw[b, b+4) (only the first n if n < 4);
 // aligned dword LDS reads + v_alignbyte (raw is 4-aligned)
@@ -982,7 +925,7 @@ __device__ __forceinline__ void g_min64(u64 *p, u64 v) {
 __device__ __forceinline__ void push_fix(const SlabParams &p, u64 start, u64 g, u32 tile) {
   const u32 i = g_add(&p.counters[2], 1u);
   if (i < p.fixcap) {
-    __attribute__((address_space(1))) u64 *f = (__attribute__((address_space(1))) u64 *)(p.fix + 3 * (u64)i);
+    gu64 *f = (gu64 *)(p.fix + (sizeof(FixRec) / sizeof(u64)) * (u64)i);
     f[0] = start; f[1] = g; f[2] = tile;  // FixRec {start, g, tile, pad}
   } else {
     g_or(&p.counters[3], 1u);  // overflow: the host re-runs the build on the general kernel
@@ -1139,21 +1082,14 @@ __device__ __forceinline__ void stage_tile(const SlabParams &p, u64 tn, u32 dst,
 // ====================================================================================
 // Per-tile results.  Every byte this pass writes is expensive next to the bytes it streams in
 // (tools/streambench.hip: 32 bytes per 16 KiB tile cost 4 % of the pass, 228 bytes 10 %), so a
-// tile writes one u64 (fq_agg[t], packed below; the scan reads its newline count) and one u16
+// tile writes one u64 (tile_agg[t]: fq_word, sidx_device.hpp; the scan reads its newline count) and one u16
 // per record (its start, bit 15 = not certified) plus the end of the last record -- a record's
 // length is the next one's start minus its own (the records of a tile are back to back).
 // Deferred records (dl[], ds[]: 2 * MAX_DEFER words per tile) are written only when a tile
 // defers.
-// (nrec: 9 bits -- a tile keeps at most RCAP records' starts, more makes it slow and nrec unused)
-constexpr u32 FQW_T = 0, FQW_GI = 16, FQW_NREC = 19, FQW_SLOW = 28, FQW_NDEF = 29;
-constexpr u32 FQW_NRECM = 0x1FF;
-constexpr u64 FQW_TMASK = 0xFFFF;  // the newline count: what the scan folds
-__device__ __forceinline__ u64 fq_word(u32 T, u32 gi0, u32 nrec, bool slow, u32 ndefer) {
-  return ((u64)T << FQW_T) | ((u64)(gi0 & 7u) << FQW_GI) | ((u64)(nrec < FQW_NRECM ? nrec : FQW_NRECM) << FQW_NREC) |
-         ((u64)(slow || nrec > (u32)RCAP) << FQW_SLOW) | ((u64)ndefer << FQW_NDEF);
-}
+// (the word: fq_word / fq_unpack, sidx_device.hpp)
 // Where a tile's u16 starts are (round 6): tile t's first FQ_LINE_E entries in one 128-byte line
-// at entry FQ_LINE_E t of fq_stage -- a dense, tile-indexed array that advances with the read
+// at entry FQ_LINE_E t of tile_stage -- a dense, tile-indexed array that advances with the read
 // stream, one full-line store per tile -- and entries FQ_LINE_E.. (tiles of more than 63
 // records; C2 has ~47 per tile) in an overflow slot of FQ_OVF entries per tile behind the lines.
 // History: a fixed 1 KiB slot per tile (round 3-4) left a partial line per tile;
@@ -1170,11 +1106,11 @@ constexpr u32 FQ_OVF = ((RCAP + 1 - FQ_LINE_E) + 7u) & ~7u;  // overflow entries
 __device__ __forceinline__ u64 fq_ovf(const SlabParams &p, u64 t) { return (u64)p.ntiles * FQ_LINE_E + t * FQ_OVF; }
 // entry L of tile t (L <= nrec: entry nrec is the end of the tile's last record)
 __device__ __forceinline__ u32 fq_start(const SlabParams &p, u64 t, u32 L) {
-  const uint16_t *s = reinterpret_cast<const uint16_t *>(p.fq_stage);
+  const uint16_t *s = reinterpret_cast<const uint16_t *>(p.tile_stage);
   return L < FQ_LINE_E ? s[t * FQ_LINE_E + L] : s[fq_ovf(p, t) + (L - FQ_LINE_E)];
 }
 constexpr u32 FQ_UNCERT = 0x8000;  // row entry: the record is not certified here
-__device__ __forceinline__ u32 *fq_defer(const SlabParams &p, u64 t) { return p.fq_tiles + t * (2 * MAX_DEFER); }
+__device__ __forceinline__ u32 *fq_defer(const SlabParams &p, u64 t) { return p.tile_words + t * (2 * MAX_DEFER); }
 
 // A workgroup keeps the lines and tile words of FQ_BLK consecutive tiles in LDS, so they leave as
 // one 2 KiB burst of lines and one 128-byte line of words per FQ_BLK tiles (profiles/r06/calls/e:
@@ -1195,7 +1131,7 @@ struct __align__(16) TilesSmem {
 // entry L of the tile being certified (batch slot j): its line in LDS, or the overflow slot
 __device__ __forceinline__ void fq_put(const SlabParams &p, TilesSmem &S, u64 t, u32 j, u32 L, uint16_t v) {
   if (L < FQ_LINE_E) S.line[j][L] = v;
-  else __builtin_nontemporal_store(v, reinterpret_cast<uint16_t *>(p.fq_stage) + fq_ovf(p, t) + (L - FQ_LINE_E));
+  else __builtin_nontemporal_store(v, reinterpret_cast<uint16_t *>(p.tile_stage) + fq_ovf(p, t) + (L - FQ_LINE_E));
 }
 
 template <bool kSpans>
@@ -1435,15 +1371,15 @@ __device__ __forceinline__ void tiles_iter(const SlabParams &p, TilesSmem &S, ui
       const u64 t0 = t - j;
       for (u32 c = (u32)lane; c < (j + 1) * (FQ_LINE_E / 8); c += 64) {
         const v4u v = *reinterpret_cast<const v4u *>(&S.line[0][0] + 8 * c);
-        __builtin_nontemporal_store(v, (__attribute__((address_space(1))) v4u *)(reinterpret_cast<uint16_t *>(p.fq_stage) +
+        __builtin_nontemporal_store(v, (__attribute__((address_space(1))) v4u *)(reinterpret_cast<uint16_t *>(p.tile_stage) +
                                                                                  t0 * FQ_LINE_E + 8 * c));
       }
       if ((u32)lane * 2 < j + 1) {  // the words, 16 bytes per lane (a last odd word alone)
         if ((u32)lane * 2 + 1 < j + 1) {
           const v4u v = *reinterpret_cast<const v4u *>(&S.words[2 * lane]);
-          *(__attribute__((address_space(1))) v4u *)(p.fq_agg + t0 + 2 * lane) = v;
+          *(__attribute__((address_space(1))) v4u *)(p.tile_agg + t0 + 2 * lane) = v;
         } else {
-          p.fq_agg[t0 + 2 * lane] = S.words[2 * lane];
+          p.tile_agg[t0 + 2 * lane] = S.words[2 * lane];
         }
       }
     }
@@ -1504,7 +1440,7 @@ __global__ __launch_bounds__(SNT, SIDX_TILES_WGS) void k_fq_tiles(const SlabPara
 constexpr u32 LCAP = TILE / 16;
 // Where a tile's positions go: each workgroup of the persistent grid appends its tiles' position
 // arrays back to back (16-byte aligned) into its own region of the stage buffer, so the stores of
-// consecutive tiles fill whole cache lines; fq_agg[t] = count | the array's offset (16-byte
+// consecutive tiles fill whole cache lines; tile_agg[t] = count | the array's offset (16-byte
 // units) << 32.  (Fixed 2 KiB slots per tile left a partial line per tile: ablating the stores
 // took 0.23-0.37 ms off the kernel, profiles/r04/ab_line_tiles_ablations.txt.)  The region of the
 // workgroup whose first tile is t0 starts where t0's would in tile order, t0 * q + min(t0, r)
@@ -1520,9 +1456,8 @@ __global__ __launch_bounds__(SNT, SIDX_LINE_WGS) void k_line_tiles(const SlabPar
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const u64 G = p.pgrid;
-  u64 t = blockIdx.x;
-  if ((G & 7) == 0) t = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
-  uint4 *stage16 = reinterpret_cast<uint4 *>(p.fq_stage);
+  u64 t = first_tile(blockIdx.x, G);
+  uint4 *stage16 = reinterpret_cast<uint4 *>(p.tile_stage);
   u64 wofs = (t * (p.ntiles / G) + (t < p.ntiles % G ? t : p.ntiles % G)) * (LCAP / 8);  // 16-byte units
   // A tile's stores leave after the next tile's DMA is issued: vmcnt counts a wave's stores as
   // well as its loads, in issue order, so stores issued before the DMA would be waited for with it
@@ -1534,7 +1469,7 @@ __global__ __launch_bounds__(SNT, SIDX_LINE_WGS) void k_line_tiles(const SlabPar
     u32 n = 0;
     if (wid == 0) {
       if (tid == 0) {
-        p.fq_agg[pt] = pword;
+        p.tile_agg[pt] = pword;
         p.pcnt[pt] = ppcnt;
       }
       n = 2;
@@ -1576,9 +1511,7 @@ __global__ __launch_bounds__(SNT, SIDX_LINE_WGS) void k_line_tiles(const SlabPar
     }
     const u32 rl = tlen > (u32)tid * 64 ? tlen - (u32)tid * 64 : 0u;
     m &= lowmask(rl);  // bytes past the slab end were zero-filled or are not this tile's
-    // the DMA range check is per dword: a partial last dword of the input came back as zeros
-    if (tlen < (u32)TILE && (tlen & 3u) && (u32)tid == ((tlen - 1) >> 6))
-      for (u32 i = tlen & ~3u; i < tlen; ++i) m |= (u64)(p.data[tlo + i] == '\n') << (i - (u32)tid * 64);
+    tail_bytes(p, tlo, tlen, tid, [&](uint8_t c, u32 bit) { m |= (u64)(c == '\n') << bit; });
     const u32 c = popc64(m);
     const u32 incl = wave_scan_add(c);
     const u32 last = m ? (u32)tid * 64 + 64 - clz64(m) : 0u;  // tile-relative '\n' + 1
@@ -1664,7 +1597,7 @@ __device__ u64 line_rows_wave(const SlabParams &p, u64 a, u64 hi, u64 carry, u64
 // one wave each; a batch whose positions do not fit LPLACE_ECAP entries places its tiles one
 // per wave from global memory.
 // SAM (F == F_SAM, k_sam_tiles): the staged positions are the tile's terminator '\n's, the
-// first one possibly not a terminator (settled by k_sam_resolve: fq_tiles bit 30); rows end at
+// first one possibly not a terminator (settled by k_sam_resolve: tile_words bit 30); rows end at
 // terminators, the row base is the SamMonoid count before the tile, dense tiles re-run two-pass.
 constexpr int LPLACE_TILES = 32;
 constexpr u32 LPLACE_ECAP = 12288;  // u16 '\n' positions staged per workgroup (24 KiB)
@@ -1680,7 +1613,7 @@ __global__ __launch_bounds__(256) void k_line_place(const SlabParams p) {
   __shared__ u64 sOff[LPLACE_TILES];    // the tile's position array in the stage buffer (16-byte units)
   __shared__ u32 sDense, sTot;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const uint16_t *stage = reinterpret_cast<const uint16_t *>(p.fq_stage);
+  const uint16_t *stage = reinterpret_cast<const uint16_t *>(p.tile_stage);
   for (u64 t0 = (u64)blockIdx.x * LPLACE_TILES; t0 < p.ntiles; t0 += (u64)gridDim.x * LPLACE_TILES) {
     if (wid == 0) {
       const u64 t = t0 + (u64)lane;
@@ -1688,7 +1621,7 @@ __global__ __launch_bounds__(256) void k_line_place(const SlabParams p) {
       u32 rows = 0, chunks = 0;
       bool dense = false;
       if (valid && F == F_SAM) {
-        const u32 w = p.fq_tiles[t], D = w & SAM_DMASK;
+        const u32 w = p.tile_words[t], D = w & SAM_DMASK;
         const u32 o = ((w & SAM_HASNL) && !(w & SAM_FIRST_TERM)) ? 1u : 0u;
         sB[lane] = SamMonoid::apply(p.state_in, p.tile_excl[t]) >> 2;
         sCar[lane] = p.ppre[t];
@@ -1699,7 +1632,7 @@ __global__ __launch_bounds__(256) void k_line_place(const SlabParams p) {
           chunks = (D + 7) / 8;
         }
       } else if (valid) {
-        const u64 w = p.fq_agg[t], T = w & LCOUNT;
+        const u64 w = p.tile_agg[t], T = w & LCOUNT;
         sOff[lane] = w >> LOFF_SHIFT;
         // row k ends at '\n' number k (rows before the slab: state_in); a slab after the first
         // drops the row open at its start through row_base (put_row)
@@ -1787,7 +1720,7 @@ __global__ void k_line_final(const SlabParams p) {
   if (threadIdx.x >= 64 || blockIdx.x) return;
   const u64 t = p.ntiles - 1;
   const u64 c = p.pcnt[t] > p.ppre[t] ? p.pcnt[t] : p.ppre[t];  // last '\n' + 1 of the slab
-  const u64 k = p.state_in + p.tile_excl[t] + (p.fq_agg[t] & LCOUNT);
+  const u64 k = p.state_in + p.tile_excl[t] + (p.tile_agg[t] & LCOUNT);
   if (c == 0 && !p.file_start) return;
   for (u64 c0 = p.n & ~15ull; c0 < p.end; c0 += 1024) {  // a slab with a halo: its first '\n'
     const u64 a = c0 + 16ull * (u64)lane;
@@ -1808,7 +1741,7 @@ __global__ void k_line_final(const SlabParams p) {
     if (lane == 0) put_row(p, k, c, p.end - c);
     return;
   }
-  if (lane == 0) g_min64(p.badkey, (k << KEY_REC_SHIFT) | ((u64)(t & ((1u << KEY_TILE_BITS) - 1)) << 4) | ST_NEEDMORE);
+  if (lane == 0) g_min64(p.badkey, bad_key(k, (u32)t, ST_NEEDMORE));
 }
 
 // ====================================================================================
@@ -1836,9 +1769,8 @@ __global__ __launch_bounds__(SNT, SIDX_LINE_WGS) void k_sam_tiles(const SlabPara
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const u64 G = p.pgrid;
-  u64 t = blockIdx.x;
-  if ((G & 7) == 0) t = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
-  uint16_t *stage = reinterpret_cast<uint16_t *>(p.fq_stage);
+  u64 t = first_tile(blockIdx.x, G);
+  uint16_t *stage = reinterpret_cast<uint16_t *>(p.tile_stage);
   for (; t < p.ntiles; t += G) {
     __builtin_amdgcn_s_setprio(3);
     stage_tile<false>(p, t, (u32)(size_t)(lds_u8 *)raw, wid, lane);
@@ -1855,19 +1787,18 @@ __global__ __launch_bounds__(SNT, SIDX_LINE_WGS) void k_sam_tiles(const SlabPara
       at |= (u64)eq16(v, '@') << (16 * j);
     }
     const u32 rl = tlen > (u32)tid * 64 ? tlen - (u32)tid * 64 : 0u;
-    // the DMA range check is per dword: a partial last dword of the input came back as zeros
-    if (tlen < (u32)TILE && (tlen & 3u) && (u32)tid == ((tlen - 1) >> 6))
-      for (u32 i = tlen & ~3u; i < tlen; ++i) {
-        const uint8_t c = p.data[tlo + i];
-        m |= (u64)(c == '\n') << (i - (u32)tid * 64);
-        at |= (u64)(c == '@') << (i - (u32)tid * 64);
-      }
+    tail_bytes(p, tlo, tlen, tid, [&](uint8_t c, u32 bit) {
+      m |= (u64)(c == '\n') << bit;
+      at |= (u64)(c == '@') << bit;
+    });
     m &= lowmask(rl);
     at &= lowmask(rl);
     const u32 len = rl < 64 ? rl : 64u;
     const u64 wi = wave_incl_scan<SamMonoid>(SamMonoid::seg(m, at, len), lane);
     // previous '\n' + 1 before this thread's word, inside the tile (0: none)
     const u32 last = m ? (u32)tid * 64 + 64 - clz64(m) : 0u;
+    // (not wave_scan_max: next to the SamMonoid scan the DPP form takes 67 VGPRs instead of 60, one
+    // workgroup per CU less)
     u32 pm = last;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -1918,9 +1849,9 @@ __global__ __launch_bounds__(SNT, SIDX_LINE_WGS) void k_sam_tiles(const SlabPara
       for (u64 kk = keep; kk; kk &= kk - 1) sp[o++] = (uint16_t)((u32)tid * 64 + ctz64(kk));
     }
     if (tid == 0) {
-      p.fq_agg[t] = agg;
+      p.tile_agg[t] = agg;
       p.pcnt[t] = LK ? tlo + LK : 0;
-      p.fq_tiles[t] = D | (anynl ? SAM_HASNL : 0u);
+      p.tile_words[t] = D | (anynl ? SAM_HASNL : 0u);
       if (D > LCAP) atomicOr(&p.counters[3], 1u);  // dense tile: re-run two-pass
     }
     lds_barrier();
@@ -1935,14 +1866,14 @@ __global__ __launch_bounds__(SNT, SIDX_LINE_WGS) void k_sam_tiles(const SlabPara
 __global__ void k_sam_resolve(const SlabParams p) {
   const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= p.ntiles) return;
-  const u32 w = p.fq_tiles[t];
+  const u32 w = p.tile_words[t];
   if (!(w & SAM_HASNL) || (w & SAM_DMASK) > LCAP) return;
   const u32 st = (u32)(SamMonoid::apply(p.state_in, p.tile_excl[t]) & 3);
   const u64 tlo = t * TILE;
   const u32 b0 = p.data[tlo];
   if (!(st == 1 || (st == 0 && b0 != '\n' && b0 != '@'))) return;
-  p.fq_tiles[t] = w | SAM_FIRST_TERM;
-  if (!p.pcnt[t]) p.pcnt[t] = tlo + reinterpret_cast<const uint16_t *>(p.fq_stage)[t * LCAP] + 1;
+  p.tile_words[t] = w | SAM_FIRST_TERM;
+  if (!p.pcnt[t]) p.pcnt[t] = tlo + reinterpret_cast<const uint16_t *>(p.tile_stage)[t * LCAP] + 1;
 }
 
 // The record after the last terminator: the rest of the file, or none when nothing is left
@@ -1951,9 +1882,9 @@ __global__ void k_sam_final(const SlabParams p) {
   if (threadIdx.x || blockIdx.x) return;
   const u64 t = p.ntiles - 1;
   const u64 c = p.pcnt[t] > p.ppre[t] ? p.pcnt[t] : p.ppre[t];  // last terminator + 1 (0: none)
-  const u64 k = SamMonoid::apply(p.state_in, SamMonoid::combine(p.tile_excl[t], p.fq_agg[t])) >> 2;
+  const u64 k = SamMonoid::apply(p.state_in, SamMonoid::combine(p.tile_excl[t], p.tile_agg[t])) >> 2;
   if (p.end > c) put_row(p, k, c, p.end - c);
-  else g_min64(p.badkey, (k << KEY_REC_SHIFT) | ((u64)(t & ((1u << KEY_TILE_BITS) - 1)) << 4) | ST_ABSENT);
+  else g_min64(p.badkey, bad_key(k, (u32)t, ST_ABSENT));
 }
 
 // k_fq_place: 64 consecutive tiles per workgroup, in three steps with one global round trip
@@ -1985,29 +1916,16 @@ __global__ __launch_bounds__(256) void k_fq_place(const SlabParams p) {
       u32 rows = 0, chunks = 0;
       u64 gbase = 0;
       if (t < p.ntiles) {
-        const u64 w = p.fq_agg[t];
-        const u32 Te = (u32)(w >> FQW_T) & 0xFFFFu;
-        const u32 gi = (u32)(w >> FQW_GI) & 7u;
-        const u32 i0 = gi == 7u ? GUESS_NONE : gi;
-        const u32 nrec = (u32)(w >> FQW_NREC) & FQW_NRECM;
-        const u32 nd = (u32)(w >> FQW_NDEF) & 0x1Fu;
-        const u64 j0 = p.state_in + p.tile_excl[t];
-        const u32 ti0 = (u32)((3 - (j0 & 3)) & 3);
-        const bool fs = p.file_start && t == 0;
-        const u32 ngt = ti0 < Te ? (Te - ti0 + 3) / 4 : 0;
-        const u32 ngg = i0 < Te ? (Te - i0 + 3) / 4 : 0;
-        const bool redo = ((w >> FQW_SLOW) & 1u) || (i0 != ti0 && (ngt | ngg) != 0);
-        if (!redo) {
-          gbase = ((j0 + ti0 + 1) >> 2) - (fs ? 1u : 0u);
-          rows = nrec;
+        const FqTileWord f = fq_unpack(p, t);
+        if (!f.redo) {
+          gbase = f.gbase;
+          rows = f.nrec;
           // starts 0..nrec (entry nrec: the last record's end): the tile's line, then its overflow
-          chunks = nrec ? (nrec + 8) / 8 : 0u;
-          if (nd) {
-            const u32 *tdef = fq_defer(p, t);
-            for (u32 i = 0; i < nd; ++i) push_fix(p, t * TILE + tdef[MAX_DEFER + i], gbase + tdef[i], (u32)t);
-          }
+          chunks = rows ? (rows + 8) / 8 : 0u;
+          const u32 *tdef = fq_defer(p, t);
+          for (u32 i = 0; i < f.nd; ++i) push_fix(p, t * TILE + tdef[MAX_DEFER + i], gbase + tdef[i], (u32)t);
         } else {
-          push_fix(p, ~0ull, j0, (u32)t);  // whole tile, true rank j0
+          push_fix(p, ~0ull, f.j0, (u32)t);  // whole tile, true rank j0
         }
       }
       const u32 ri = wave_scan_add(rows), ci = wave_scan_add(chunks);
@@ -2025,8 +1943,8 @@ __global__ __launch_bounds__(256) void k_fq_place(const SlabParams p) {
       const u32 e0 = sE[k], nch = (sE[k + 1] - e0) >> 3;
       const u64 tk = t0 + (u64)k;
       // chunks 0..7: the tile's line; 8..: its overflow slot (two loads in flight per step)
-      const uint4 *ln = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(p.fq_stage) + tk * FQ_LINE_E);
-      const uint4 *ov = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(p.fq_stage) + fq_ovf(p, tk)) -
+      const uint4 *ln = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(p.tile_stage) + tk * FQ_LINE_E);
+      const uint4 *ov = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(p.tile_stage) + fq_ovf(p, tk)) -
                         FQ_LINE_E / 8;
       u32 c = (u32)(lane & 3);
       for (; c + 4 < nch; c += 8) {
@@ -2089,20 +2007,11 @@ __global__ __launch_bounds__(256) void k_fq_spans_place(const SlabParams p, u32 
   const int lane = threadIdx.x & 63;
   const u64 nw = (u64)gridDim.x * 4;
   for (u64 t = (u64)blockIdx.x * 4 + (threadIdx.x >> 6); t < p.ntiles; t += nw) {
-    const u64 w = p.fq_agg[t];
-    const u32 Te = (u32)(w >> FQW_T) & 0xFFFFu;
-    const u32 gi = (u32)(w >> FQW_GI) & 7u;
-    const u32 i0 = gi == 7u ? GUESS_NONE : gi;
-    const u32 nrec = (u32)(w >> FQW_NREC) & FQW_NRECM;
-    const u64 j0 = p.state_in + p.tile_excl[t];
-    const u32 ti0 = (u32)((3 - (j0 & 3)) & 3);
-    const u32 ngt = ti0 < Te ? (Te - ti0 + 3) / 4 : 0;
-    const u32 ngg = i0 < Te ? (Te - i0 + 3) / 4 : 0;
-    if (((w >> FQW_SLOW) & 1u) || (i0 != ti0 && (ngt | ngg) != 0)) continue;  // the whole tile went to k_fixup
-    const u64 gbase = ((j0 + ti0 + 1) >> 2) - ((p.file_start && t == 0) ? 1u : 0u);
+    const FqTileWord f = fq_unpack(p, t);
+    if (f.redo) continue;  // the whole tile went to k_fixup
     const uint16_t *ln = p.fq_lines + t * (3 * RCAP);
-    for (u32 L = (u32)lane; L < nrec; L += 64) {
-      const u64 g = gbase + L;
+    for (u32 L = (u32)lane; L < f.nrec; L += 64) {
+      const u64 g = f.gbase + L;
       const u32 rv = fq_start(p, t, L);
       if (g < p.row_base || g - p.row_base >= K || (rv & FQ_UNCERT)) continue;
       const u32 x0 = ln[3 * L];
@@ -2130,7 +2039,7 @@ __device__ __forceinline__ void fix_record(const SlabParams &p, u64 s, u64 g, u3
   const u32 st = run_record_cold<F_FASTQ>(wa, s, 0, len, epos, elen);
   if (lane == 0) {
     if (st == ST_OK) put_row(p, g, s, len);
-    else atomicMin(p.badkey, (g << KEY_REC_SHIFT) | ((u64)(tile & ((1u << KEY_TILE_BITS) - 1)) << 4) | st);
+    else atomicMin(p.badkey, bad_key(g, tile, st));
   }
 }
 
@@ -2179,12 +2088,7 @@ __global__ __launch_bounds__(256) void k_fixup(const SlabParams p, DevResult *re
       u32 m = 0;
       if (a < thi) m = eq16((a + 16 <= thi) ? load16(p.data + a) : load16_partial(p.data, a, thi), '\n');
       const u32 c = __popc(m);
-      u32 incl = c;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const u32 y = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += y;
-      }
+      const u32 incl = wave_scan_add(c);
       u64 cand = __ballot(m != 0);
       while (cand) {
         const int L = (int)ctz64(cand);
@@ -2233,7 +2137,7 @@ constexpr u32 FA_OK = 0, FA_INV = 1, FA_DEFER = 2, FA_SKIP = 3;  // SKIP: owned 
 constexpr int FA_NLW = 2;
 constexpr u32 FA_NONE = ~0u;
 constexpr int FAW = 8;  // rare tile words: -, -, -, -, finv, inv_lo (a tile with an invalid piece), eof_st, eof_lo (the last tile)
-// The per-tile word (fq_agg[t]): the FastaMonoid aggregate in bits 0-17 (what the scan folds),
+// The per-tile word (tile_agg[t]): the FastaMonoid aggregate in bits 0-17 (what the scan folds),
 // the candidate count, slow / conditional-first flags, the first conditional and the first
 // definite boundary (15 bits each, 0x7FFF: none) and whether tw[4..5] hold an invalid piece --
 // one u64 store per tile instead of a 32-byte record (the k_fq_tiles note on stores).
@@ -2430,7 +2334,7 @@ __device__ __forceinline__ void fa_iter(const SlabParams &p, FaSmem &S, uint8_t 
   // ---- validation of the pieces that close at the candidates -------------------------------
   __builtin_amdgcn_s_setprio(2);
   const bool slow = ncand > (u32)RCAP;
-  uint16_t *stage = reinterpret_cast<uint16_t *>(p.fq_stage + t * RCAP);  // position | status << 14
+  uint16_t *stage = reinterpret_cast<uint16_t *>(p.tile_stage + t * RCAP);  // position | status << 14
   // A slab after the file's first: its first tile's first boundary (the incoming state is known
   // there) closes the record open at the slab start, which the previous slab owns and checks
   // through its halo; any other piece starting before data[0] is checked as a part (never INV).
@@ -2448,7 +2352,7 @@ __device__ __forceinline__ void fa_iter(const SlabParams &p, FaSmem &S, uint8_t 
       if (st == FA_INV) atomicMin(&S.finv, i);
     }
   }
-  u32 *tw = p.fq_tiles + t * FAW;
+  u32 *tw = p.tile_words + t * FAW;
   if (tid == SNT - 1) {  // the certificate of the piece open at the tile's end (fa_w_tcert)
     // (the first '\n' after the last '>': two mask words in one LDS round, the loop beyond)
     const u32 wi = alast >> 6;
@@ -2476,7 +2380,7 @@ __device__ __forceinline__ void fa_iter(const SlabParams &p, FaSmem &S, uint8_t 
     const u32 finv = S.finv;
     const u64 word = fa_word(A, ncand, slow, delta, delta ? (S.cand[0] & 0x3FFFu) : FA_NONE,
                              (A >> 3) ? (S.cand[delta] & 0x3FFFu) : FA_NONE, finv != FA_NONE, S.tcert != 0);
-    if (tid == 0) p.fq_agg[t] = word;
+    if (tid == 0) p.tile_agg[t] = word;
     if (tid == 0 && finv != FA_NONE) {
       tw[4] = finv;
       tw[5] = S.cand[finv] >> 14;
@@ -2505,9 +2409,6 @@ __global__ __launch_bounds__(SNT, SIDX_FA_WGS) void k_fa_tiles(const SlabParams 
   }
 }
 
-__device__ __forceinline__ u64 fa_key(u64 k, u32 slot, u32 st) {
-  return (k << KEY_REC_SHIFT) | ((u64)(slot & ((1u << KEY_TILE_BITS) - 1)) << 4) | st;
-}
 // first boundary of tile u given its words and entering state: the conditional '>' when the
 // tile is entered armed, else its first definite boundary (FA_NONE: none)
 __device__ __forceinline__ u32 fa_first(u32 flags, u32 fc, u32 fd, u64 st) {
@@ -2519,7 +2420,7 @@ __device__ u64 fa_next_global(const SlabParams &p, u64 u, int lane) {
     const u64 v = u + (u64)lane;
     u32 f = FA_NONE;
     if (v < p.ntiles) {
-      const u64 w = p.fq_agg[v];
+      const u64 w = p.tile_agg[v];
       f = fa_first(fa_w_flags(w), fa_w_fc(w), fa_w_fd(w), FastaMonoid::apply(p.state_in, p.tile_excl[v]));
     }
     const u64 bal = __ballot(f != FA_NONE);
@@ -2542,11 +2443,11 @@ __global__ __launch_bounds__(256) void k_fa_place(const SlabParams p) {
   for (u64 t0 = (u64)blockIdx.x * PLACE_TILES; t0 < p.ntiles; t0 += (u64)gridDim.x * PLACE_TILES) {
     if (tid >= 128 && tid < 128 + PLACE_TILES) {
       const u64 u = t0 + (u64)(tid - 128);  // the tile before t0 + (tid - 128), plus one
-      sC[tid - 128] = (u >= 1 && u - 1 < p.ntiles) ? (u32)fa_w_tcert(p.fq_agg[u - 1]) : 0u;
+      sC[tid - 128] = (u >= 1 && u - 1 < p.ntiles) ? (u32)fa_w_tcert(p.tile_agg[u - 1]) : 0u;
     }
     if (tid <= PLACE_TILES && t0 + tid < p.ntiles) {
-      const u64 w = p.fq_agg[t0 + tid];
-      const u32 *tw = p.fq_tiles + (t0 + tid) * FAW;
+      const u64 w = p.tile_agg[t0 + tid];
+      const u32 *tw = p.tile_words + (t0 + tid) * FAW;
       const bool last = t0 + tid == p.ntiles - 1;
       sw[tid][0] = make_uint4((u32)(w >> 18) & 0xFFFu, fa_w_flags(w), fa_w_fc(w), fa_w_fd(w));
       sw[tid][1] = make_uint4((w >> 63) ? tw[4] : FA_NONE, (w >> 63) ? tw[5] : 0u, last ? tw[6] : FA_OK,
@@ -2568,7 +2469,7 @@ __global__ __launch_bounds__(256) void k_fa_place(const SlabParams p) {
       const u64 cnt = st >> 1;
       const u64 tlo = t * TILE;
       if (p.n == 0) {  // no record at all: (0, EOF) on record 0
-        if (lane == 0 && p.file_start) g_min64(p.badkey, fa_key(0, 0, ST_ABSENT));
+        if (lane == 0 && p.file_start) g_min64(p.badkey, bad_key(0, 0, ST_ABSENT));
         continue;
       }
       // too many candidates for the table: the whole tile from global memory
@@ -2594,7 +2495,7 @@ __global__ __launch_bounds__(256) void k_fa_place(const SlabParams p) {
         const u64 r = fa_next_global(p, tt + 2, lane);
         if (sub == (L >> 4)) nxt = r;
       }
-      const uint16_t *stage = reinterpret_cast<const uint16_t *>(p.fq_stage + t * RCAP);
+      const uint16_t *stage = reinterpret_cast<const uint16_t *>(p.tile_stage + t * RCAP);
       // the record open at a slab's start (number s0) is the previous slab's: no report of the
       // piece that closes it; if that was the tile's first invalid piece, the later invalid
       // ones of the tile go to k_fa_fixup (their piece starts are not kept)
@@ -2614,7 +2515,7 @@ __global__ __launch_bounds__(256) void k_fa_place(const SlabParams p) {
         } else if (vs == FA_INV && idx == finv) {  // the tile's first invalid piece
           p.detail[2 * t] = p.base + tlo + invlo;  // file offsets (slabs: base)
           p.detail[2 * t + 1] = g + 1 - invlo;  // the piece includes its '>'
-          g_min64(p.badkey, fa_key(k2, (u32)t, ST_FA_INVALID));
+          g_min64(p.badkey, bad_key(k2, (u32)t, ST_FA_INVALID));
         }
         const u64 e = (i + 1 < nb) ? tlo + (stage[idx + 1] & 0x3FFFu) : nxt;
         if (e == p.n && p.end > p.n) push_fix(p, tlo + g, k2 + 1, (u32)t | FIX_HALO);  // ends past the slab
@@ -2631,7 +2532,7 @@ __global__ __launch_bounds__(256) void k_fa_place(const SlabParams p) {
           const u32 slot = p.ntiles;
           p.detail[2 * (u64)slot] = p.base + tlo + elo;
           p.detail[2 * (u64)slot + 1] = p.n - tlo - elo;
-          g_min64(p.badkey, fa_key(k2, slot, ST_FA_INVALID));
+          g_min64(p.badkey, bad_key(k2, slot, ST_FA_INVALID));
         } else if (est == FA_DEFER) {
           push_fix(p, p.n, k2, (u32)t);
         }
@@ -2670,7 +2571,7 @@ __device__ __forceinline__ void fa_report(const SlabParams &p, u64 k, u32 slot, 
   if (lane == 0) {
     p.detail[2 * (u64)slot] = p.base + epos;  // file offset
     p.detail[2 * (u64)slot + 1] = elen;
-    g_min64(p.badkey, fa_key(k, slot, ST_FA_INVALID));
+    g_min64(p.badkey, bad_key(k, slot, ST_FA_INVALID));
   }
 }
 
@@ -2682,7 +2583,7 @@ __device__ __forceinline__ void fa_report(const SlabParams &p, u64 k, u32 slot, 
 // boundary that does not reach EOF is ST_NEEDMORE (the slab protocol's "halo exhausted").
 __device__ void fa_halo_close(const SlabParams &p, u64 b, u64 k, u32 slot, int lane) {
   const u64 nt = p.ntiles;
-  u32 armed = (u32)(FastaMonoid::apply(FastaMonoid::apply(p.state_in, p.tile_excl[nt - 1]), p.fq_agg[nt - 1] & FAW_AMASK) & 1);
+  u32 armed = (u32)(FastaMonoid::apply(FastaMonoid::apply(p.state_in, p.tile_excl[nt - 1]), p.tile_agg[nt - 1] & FAW_AMASK) & 1);
   WaveAcc wa;
   wa.g = p.data; wa.end = p.end; wa.eof = p.eof; wa.lane = lane; wa.front = p.front;
   u64 g = ~0ull;
@@ -2725,7 +2626,7 @@ __device__ void fa_halo_close(const SlabParams &p, u64 b, u64 k, u32 slot, int l
     }
   }
   if (g == ~0ull && !p.eof) {
-    if (lane == 0) g_min64(p.badkey, fa_key(k, slot, ST_NEEDMORE));
+    if (lane == 0) g_min64(p.badkey, bad_key(k, slot, ST_NEEDMORE));
     return;
   }
   const u64 e = g == ~0ull ? p.end : g;
@@ -2924,272 +2825,6 @@ __device__ __forceinline__ void finalize_body(const SlabParams &p, int fmt, DevR
 }
 
 // ====================================================================================
-// Multi-GPU slabs: guess a slab's incoming state, fold the gathered summaries
-// ====================================================================================
-// FASTQ: the first line of the slab that looks like a record start ('@' line, '+' two
-// lines later, sequence and quality lines of equal length) fixes the line phase.
-// FASTA: '\n' vs '>' closest before the slab start (armed bit).  SAM: class of the line
-// open at the slab start.  LINE: nothing to guess.  One wave; verified after the exchange.
-__global__ void k_slab_guess(const uint8_t *data, u64 n, u64 front, int fmt, u64 *out) {
-  __shared__ u32 nlp[256];
-  __shared__ u32 cnt;
-  const int lane = threadIdx.x;
-  u64 guess = 0;
-  if (fmt == F_FASTQ) {
-    const u64 lim = n < 4096 ? n : 4096;
-    if (lane == 0) cnt = 0;
-    __syncthreads();
-    for (u64 b = 0; b < lim; b += 1024) {  // '\n' positions of the first 4 KiB, in order
-      const u64 a = b + (u64)lane * 16;
-      u32 m = 0;
-      if (a < lim) m = eq16((a + 16 <= lim) ? load16(data + a) : load16_partial(data, a, lim), '\n');
-      const u32 c = __popc(m);
-      u32 pre = c;
-      for (int d = 1; d < 64; d <<= 1) { const u32 y = __shfl_up(pre, d, 64); if (lane >= d) pre += y; }
-      const u32 base = cnt;
-      u32 o = base + pre - c;
-      while (m) { if (o < 256) nlp[o] = (u32)(a + __builtin_ctz(m)); ++o; m &= m - 1; }
-      __syncthreads();
-      if (lane == 63) cnt = base + pre;
-      __syncthreads();
-    }
-    const u32 N = cnt < 256 ? cnt : 256;
-    // candidate i: record starts after '\n' #i (local rank i): lines (i,i+1],(i+1,i+2]...
-    bool ok = false;
-    for (u32 i0 = 0; i0 + 4 < N; i0 += 64) {
-      const u32 i = i0 + lane;
-      ok = false;
-      if (i + 4 < N) {
-        const u32 s = nlp[i] + 1, e0 = nlp[i + 1], e1 = nlp[i + 2], e2 = nlp[i + 3], e3 = nlp[i + 4];
-        ok = data[s] == '@' && e0 > s + 1 && data[e1 + 1] == '+' && (e1 - e0) == (e3 - e2) && e1 > e0 + 1;
-      }
-      const u64 bal = __ballot(ok);
-      if (bal) { const u32 L = ctz64(bal); guess = (3u - ((i0 + L) & 3)) & 3; break; }
-    }
-  } else if (fmt == F_FASTA || fmt == F_SAM) {
-    // closest '\n' / '>' before data[0] within `front` bytes (scan backwards 1 KiB per step)
-    const u64 lim = front < 65536 ? front : 65536;
-    i64 best = -1;
-    u32 bestc = 0;
-    for (u64 b = 0; b < lim && best < 0; b += 1024) {
-      // window [-(b+1024), -b): lane k holds bytes [-(b+16k+16), -(b+16k))
-      const u64 hi = b + (u64)lane * 16;  // distance of this chunk's end before data[0]
-      u32 nlm = 0, gtm = 0;
-      if (hi < lim) {
-        const u64 take = (lim - hi) < 16 ? (lim - hi) : 16;
-        const uint8_t *q = data - hi - take;
-        const uint4 v = load16_partial(q, 0, take);
-        nlm = eq16(v, '\n');
-        gtm = fmt == F_FASTA ? eq16(v, '>') : 0u;
-        // bit j <-> byte at distance hi + take - j before data[0]
-        const u32 m = nlm | gtm;
-        if (m) {
-          const u32 j = 31 - __builtin_clz(m);           // closest to data[0]
-          const u64 dist = hi + take - j;                 // >= 1
-          const u64 key = (dist << 1) | ((gtm >> j) & 1);
-          (void)key;
-        }
-      }
-      const u32 m = nlm | gtm;
-      const u64 bal = __ballot(m != 0);
-      if (bal) {
-        const int L = (int)ctz64(bal);  // nearest chunk first
-        const u32 mm = __shfl(m, L, 64);
-        const u32 g = __shfl(gtm, L, 64);
-        const u64 hiL = b + (u64)L * 16;
-        const u64 takeL = (lim - hiL) < 16 ? (lim - hiL) : 16;
-        const u32 j = 31 - __builtin_clz(mm);
-        best = (i64)(hiL + takeL - j);
-        bestc = (g >> j) & 1;  // 1: the nearest is '>'
-      }
-    }
-    if (fmt == F_FASTA) {
-      guess = (best < 0) ? 1 : (bestc ? 0 : 1);  // state = count 0 << 1 | armed
-    } else {
-      // SAM: byte before data[0] is '\n' -> FRESH; else class of the byte after the nearest '\n'
-      if (front == 0 || best == 1) guess = 0;
-      else if (best < 0) guess = 1;
-      else guess = (data[-(best - 1)] == '@') ? 2 : 1;
-    }
-  }
-  if (lane == 0) *out = guess;
-}
-
-template <int F>
-__device__ __forceinline__ bool slab_compatible(u64 truth, u64 guess) {
-  if (F == F_FASTQ) return (truth & 3) == (guess & 3);
-  if (F == F_FASTA) return (truth & 1) == (guess & 1);
-  if (F == F_SAM) return (truth & 3) == (guess & 3);
-  return true;
-}
-template <int F>
-__device__ __forceinline__ u64 slab_delta(u64 truth, u64 guess) {  // global - local record numbers
-  if (F == F_FASTQ) return (truth - (guess & 3)) >> 2;
-  if (F == F_FASTA) return (truth >> 1) - (guess >> 1);
-  if (F == F_SAM) return (truth >> 2) - (guess >> 2);
-  return truth - guess;
-}
-
-// The caller's expected build tag of every slab's summary (shockidx_slab_combine's expect_seq).
-struct SeqExpect {
-  u32 v[32];
-  u32 on;
-};
-template <int F>
-__device__ void slab_combine(const SlabSummary *all, int world, int rank, const SeqExpect &ex, SlabPlan *out) {
-  typedef typename Traits<F>::M M;
-  SlabPlan pl;
-  pl.inconsistent = 0; pl.flags = 0; pl.err_rank = -1; pl.err_pos = 0; pl.err_len = 0; pl.code = ST_OK;
-  pl.count = 0; pl.state_in = 0; pl.first_record = 0;
-  u64 s = 0;  // state before slab 0 (file start)
-  bool done = false;
-  for (int q = 0; q < world; ++q) {
-    const SlabSummary &x = all[q];
-    if (ex.on && x.seq != ex.v[q]) pl.flags |= 32;  // a stale summary: never folded into a result
-    const bool ok = slab_compatible<F>(s, x.state_in);
-    if (!ok) pl.inconsistent |= 1u << q;
-    const u64 delta = slab_delta<F>(s, x.state_in);
-    if (q == rank) { pl.state_in = s; pl.first_record = delta + x.row_base; }
-    pl.flags |= x.flags & ~RF_CAPACITY;
-    if (!done && ok) {
-      if (x.key != KEY_NONE) {
-        pl.count = (x.key >> KEY_REC_SHIFT) + delta;
-        pl.code = (u32)(x.key & 15);
-        if (pl.code == ST_FA_INVALID) { pl.err_rank = q; pl.err_pos = x.err_pos; pl.err_len = x.err_len; }
-        done = true;
-      } else if (q == world - 1) {
-        pl.count = x.natural + delta;
-      }
-    }
-    s = M::apply(s, x.agg);
-  }
-  *out = pl;
-}
-
-__global__ void k_slab_combine(const SlabSummary *all, int world, int rank, int fmt, const SeqExpect ex, SlabPlan *out) {
-  if (threadIdx.x || blockIdx.x) return;
-  if (fmt == F_FASTQ) slab_combine<F_FASTQ>(all, world, rank, ex, out);
-  else if (fmt == F_FASTA) slab_combine<F_FASTA>(all, world, rank, ex, out);
-  else if (fmt == F_SAM) slab_combine<F_SAM>(all, world, rank, ex, out);
-  else slab_combine<F_LINE>(all, world, rank, ex, out);
-}
-
-// ====================================================================================
-// k_detect: multi.go:43-62 over the zero-padded first 32768 bytes (fasta, fastq, sam)
-// ====================================================================================
-struct DetBuf {
-  const uint8_t *d;  // the zero-padded 32768-byte head, staged in LDS
-  __device__ __forceinline__ u32 at(u64 i) const { return d[i]; }
-};
-__device__ __forceinline__ bool dS(u32 c) { return !(c == '\t' || c == '\n' || c == '\f' || c == '\r' || c == ' '); }
-__device__ __forceinline__ bool dSST(u32 c) { return !(c == '\n' || c == '\f' || c == '\r'); }
-__device__ __forceinline__ bool dNR(u32 c) { return c == '\n' || c == '\r'; }
-__device__ __forceinline__ bool dAlpha(u32 c) { return (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z'); }
-
-// The matchers run wave-wide: every "class run" of the regex is skipped 64 bytes at a time
-// (one byte per lane, a ballot for the first byte outside the class); single-byte checks are
-// uniform LDS reads.  skip(b, i, P): the first j >= i with !P(b[j]), N if none.
-template <class P>
-__device__ __forceinline__ u64 det_skip(const DetBuf &b, u64 i, P pred) {
-  const u64 N = 32768;
-  const int lane = threadIdx.x & 63;
-  for (u64 base = i; base < N; base += 64) {
-    const u64 q = base + (u64)lane;
-    const u64 m = __ballot(q < N && !pred(b.at(q)));
-    if (m) return base + (u64)__builtin_ctzll(m);
-  }
-  return N;
-}
-__device__ __forceinline__ bool dLetDash(u32 c) { return dAlpha(c) || c == '-'; }
-
-// fasta.go:22  ^[\n\r]*>\S+[\S\t ]*[\n\r]+[A-Za-z\- ]+
-__device__ bool det_fasta(const DetBuf &b) {
-  const u64 N = 32768;
-  u64 i = det_skip(b, 0, dNR);
-  if (i >= N || b.at(i) != '>') return false;
-  ++i;
-  if (i >= N || !dS(b.at(i))) return false;
-  i = det_skip(b, i + 1, dSST);
-  if (i >= N || !dNR(b.at(i))) return false;
-  i = det_skip(b, i, dNR);
-  if (i >= N) return false;
-  const u32 c = b.at(i);
-  return dAlpha(c) || c == '-' || c == ' ';
-}
-// fastq.go:22  ^[\n\r]*@\S+[\S\t ]*[\n\r]+[A-Za-z\-]+[\n\r]+\+[\S\t ]*[\n\r]+\S*[\n\r]+
-__device__ bool det_fastq(const DetBuf &b) {
-  const u64 N = 32768;
-  u64 i = det_skip(b, 0, dNR);
-  if (i >= N || b.at(i) != '@') return false;
-  ++i;
-  if (i >= N || !dS(b.at(i))) return false;
-  i = det_skip(b, i + 1, dSST);
-  if (i >= N || !dNR(b.at(i))) return false;
-  i = det_skip(b, i, dNR);
-  if (i >= N || !dLetDash(b.at(i))) return false;
-  i = det_skip(b, i, dLetDash);
-  if (i >= N || !dNR(b.at(i))) return false;
-  i = det_skip(b, i, dNR);
-  if (i >= N || b.at(i) != '+') return false;
-  i = det_skip(b, i + 1, dSST);
-  const u64 k = det_skip(b, i, dNR) - i;
-  if (k == 0) return false;
-  if (k >= 2) return true;
-  i = det_skip(b, i + 1, dS);
-  return i < N && dNR(b.at(i));
-}
-// sam.go:17  ^[\n\r]*[@[A-Z][A-Z][ \t]+[\S \t]+[\n\r]]*
-__device__ bool det_sam(const DetBuf &b) {
-  const u64 N = 32768;
-  u64 i = det_skip(b, 0, dNR);
-  if (i >= N) return false;
-  u32 c = b.at(i);
-  if (!(c == '@' || c == '[' || (c >= 'A' && c <= 'Z'))) return false;
-  ++i;
-  c = b.at(i);
-  if (i >= N || !(c >= 'A' && c <= 'Z')) return false;
-  ++i;
-  c = b.at(i);
-  if (i >= N || !(c == ' ' || c == '\t')) return false;
-  ++i;
-  const u64 e = det_skip(b, i, dSST);
-  return e > i && e < N && dNR(b.at(e));
-}
-
-// The head is staged into LDS by the whole workgroup (16 B per lane, every load in flight at
-// once), then three waves run the three matchers against LDS.
-constexpr int DET_THREADS = 512;
-__global__ __launch_bounds__(DET_THREADS) void k_detect(const uint8_t *data, u64 n, int *out) {
-  __shared__ __align__(16) uint8_t head[32768];
-  const u64 m = n < 32768 ? n : 32768;
-  constexpr int PER = 32768 / 16 / DET_THREADS;
-  uint4 v[PER];  // every load in flight before the first LDS store
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const u64 a = (u64)(threadIdx.x + k * DET_THREADS) * 16;
-    v[k] = make_uint4(0, 0, 0, 0);
-    if (a + 16 <= m) v[k] = load16(data + a);
-    else if (a < m) v[k] = load16_partial(data, a, m);
-  }
-#pragma unroll
-  for (int k = 0; k < PER; ++k) *reinterpret_cast<uint4 *>(&head[(u64)(threadIdx.x + k * DET_THREADS) * 16]) = v[k];
-  __syncthreads();
-  // the three matchers, one per wave (side by side), each wave-wide
-  __shared__ int part[3];
-  const DetBuf b{head};
-  if (threadIdx.x < 192) {
-    const int w = threadIdx.x >> 6;
-    const int r = w == 0 ? (det_fasta(b) ? 1 : 0) : w == 1 ? (det_fastq(b) ? 2 : 0) : (det_sam(b) ? 4 : 0);
-    if ((threadIdx.x & 63) == 0) part[w] = r;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  const int mk = part[0] | part[1] | part[2];
-  out[0] = (mk & 1) ? F_FASTA : (mk & 2) ? F_FASTQ : (mk & 4) ? F_SAM : F_NONE;
-  out[1] = mk;
-}
-
-// ====================================================================================
 // k_scan_excl<M>: the device-wide exclusive scan of the per-tile monoid aggregates -- the
 // parallel form of record.go:76's serial `curr += int64(n)` (the global record number of a
 // tile's first record is the fold of everything before it).  Single pass, decoupled
@@ -3280,16 +2915,11 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_excl(const u64 *agg, u64 *excl,
 }  // namespace sidx
 
 // ====================================================================================
-// Host launch wrappers (internal to libshockidx; the C ABI lives in sidx_capi.cpp)
+// Host launch wrappers (internal to libshockidx, declared in sidx_launch.hpp; the build path is
+// chosen in sidx_build.cpp, the control kernels' launchers are in sidx_control.hip)
 // ====================================================================================
 using namespace sidx;
 
-extern "C" hipError_t sidx_launch_detect(const uint8_t *d, u64 n, int *d_out, hipStream_t s) {
-  hipLaunchKernelGGL(k_detect, dim3(1), dim3(DET_THREADS), 0, s, d, n, d_out);
-  return hipGetLastError();
-}
-
-// look-back words of the scans: two arrays of the status block (SlabParams::scan_look)
 namespace {
 // The persistent grid of a tile kernel: CUs x its own co-resident workgroups (the launch
 // parameters' pgrid is sized for k_fq_tiles; a larger grid than fits would leave the extra
@@ -3299,10 +2929,10 @@ int occupancy(K kern) {
   int n = 0;
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, SNT, 0) == hipSuccess && n > 0 ? n : 1;
 }
-u32 tile_grid(const SlabParams &p, int which) {
+u32 tile_grid(const SlabParams &p, TilePass pass) {
   // cached per device and kernel; written from the multi-device slab threads at once, so the
   // cache words are atomics (a repeated query stores the same value)
-  static std::atomic<int> occ[4], cus[64];
+  static std::atomic<int> occ[TP_SAM + 1], cus[64];
   int dev = 0;
   (void)hipGetDevice(&dev);
   std::atomic<int> &cu_slot = cus[dev & 63];
@@ -3311,14 +2941,20 @@ u32 tile_grid(const SlabParams &p, int which) {
     (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
     cu_slot.store(cu, std::memory_order_relaxed);
   }
-  int oc = occ[which].load(std::memory_order_relaxed);
+  int oc = occ[pass].load(std::memory_order_relaxed);
   if (!oc) {
-    oc = which == 1 ? occupancy(k_fa_tiles) : which == 3 ? occupancy(k_sam_tiles) : occupancy(k_line_tiles);
-    occ[which].store(oc, std::memory_order_relaxed);
+    oc = pass == TP_FA ? occupancy(k_fa_tiles) : pass == TP_SAM ? occupancy(k_sam_tiles) : occupancy(k_line_tiles);
+    occ[pass].store(oc, std::memory_order_relaxed);
   }
   const u64 g = (u64)(cu > 0 ? cu : 1) * (u64)(oc > 0 ? oc : 1);
   return (u32)(g < p.ntiles ? g : p.ntiles);
 }
+// grid of a placement kernel that takes `per` tiles per workgroup and strides by its grid
+u32 place_grid(u64 ntiles, u64 per) {
+  const u64 g = (ntiles + per - 1) / per;
+  return (u32)(g < 65536 ? g : 65536);
+}
+// look-back words of the scans: two arrays of the status block (SlabParams::scan_look)
 template <class M>
 hipError_t scan_excl(const SlabParams &p, const u64 *agg, u64 *excl, int which, bool total, hipStream_t s,
                      u64 in_mask = ~0ull) {
@@ -3328,189 +2964,128 @@ hipError_t scan_excl(const SlabParams &p, const u64 *agg, u64 *excl, int which, 
                      p.epoch, in_mask, p.gate, p.gate_fmt);
   return hipGetLastError();
 }
-}  // namespace
-
-// Two-pass index (SAM; FASTA and line slabs; the general re-run): pass 1 (tile aggregates,
-// their exclusive scan, the slab aggregate) then k_index1 with every tile's incoming state.
-extern "C" hipError_t sidx_launch_index(int fmt, const SlabParams *pp, DevResult *d_res, hipStream_t s,
-                                        hipEvent_t ek0, hipEvent_t ek1) {
-  const SlabParams &p = *pp;
-  u64 *agg = p.fq_agg, *excl = (u64 *)p.tile_excl;
-  const dim3 g1(p.ntiles), block(NTHREADS);
-  if (ek0) (void)hipEventRecord(ek0, s);
-  hipError_t e = hipSuccess;
-  switch (fmt) {
-    case F_FASTQ: hipLaunchKernelGGL(k_tile_agg<F_FASTQ>, g1, block, 0, s, p, agg); e = scan_excl<CountMonoid>(p, agg, excl, 0, true, s); break;
-    case F_FASTA: hipLaunchKernelGGL(k_tile_agg<F_FASTA>, g1, block, 0, s, p, agg); e = scan_excl<FastaMonoid>(p, agg, excl, 0, true, s); break;
-    case F_SAM: hipLaunchKernelGGL(k_tile_agg<F_SAM>, g1, block, 0, s, p, agg); e = scan_excl<SamMonoid>(p, agg, excl, 0, true, s); break;
-    case F_LINE: hipLaunchKernelGGL(k_tile_agg<F_LINE>, g1, block, 0, s, p, agg); e = scan_excl<CountMonoid>(p, agg, excl, 0, true, s); break;
-    default: return hipErrorInvalidValue;
-  }
+hipError_t finalize(const SlabParams &p, int fmt, DevResult *d_res, hipStream_t s) {
+  hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  switch (fmt) {
-    case F_FASTQ: hipLaunchKernelGGL(k_index1<F_FASTQ>, g1, block, 0, s, p); break;
-    case F_FASTA: hipLaunchKernelGGL(k_index1<F_FASTA>, g1, block, 0, s, p); break;
-    case F_SAM: hipLaunchKernelGGL(k_index1<F_SAM>, g1, block, 0, s, p); break;
-    case F_LINE: hipLaunchKernelGGL(k_index1<F_LINE>, g1, block, 0, s, p); break;
-  }
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  if (ek1) (void)hipEventRecord(ek1, s);
   hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, p, fmt, d_res);
   return hipGetLastError();
 }
 
-extern "C" hipError_t sidx_launch_slab_guess(const uint8_t *d, u64 n, u64 front, int fmt, u64 *d_out,
-                                             hipStream_t s) {
-  hipLaunchKernelGGL(k_slab_guess, dim3(1), dim3(64), 0, s, d, n, front, fmt, d_out);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t sidx_launch_slab_combine(const void *d_all, int world, int rank, int fmt, const uint32_t *expect,
-                                               void *d_plan, hipStream_t s) {
-  SeqExpect ex;
-  memset(&ex, 0, sizeof ex);
-  if (expect) {
-    ex.on = 1;
-    for (int q = 0; q < world && q < 32; ++q) ex.v[q] = expect[q];
-  }
-  hipLaunchKernelGGL(k_slab_combine, dim3(1), dim3(64), 0, s, (const SlabSummary *)d_all, world, rank, fmt, ex,
-                     (SlabPlan *)d_plan);
-  return hipGetLastError();
-}
-
-// Whole-table check (SHOCKIDX_VERIFY builds, on in the GPU test suite): every row starts where
-// the previous one ends (record.go:51-83), over the rows the build reported (DevResult::count,
-// read on the device after the pipeline); a violation sets the internal-error flag.
-__global__ __launch_bounds__(256) void k_verify_rows(const u64 *rows, u64 row_base, u64 row_cap, DevResult *res) {
-  const DevResult r = *res;
-  if (r.flags & (RF_CAPACITY | RF_MISSPEC)) return;  // a capacity overflow or a failed speculation: re-run anyway
-  const u64 nr = r.count > row_base ? r.count - row_base : 0;
-  const u64 n = nr < row_cap ? nr : row_cap;
-  bool bad = false;
-  for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i + 1 < n; i += (u64)gridDim.x * 256) {
-    const ulonglong2 a = reinterpret_cast<const ulonglong2 *>(rows)[i];
-    bad |= a.x + a.y != rows[2 * (i + 1)];
-  }
-  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&res->flags, RF_INTERNAL);
-}
-extern "C" hipError_t sidx_launch_verify_rows(const u64 *rows, u64 row_base, u64 row_cap, DevResult *d_res, hipStream_t s) {
-  hipLaunchKernelGGL(k_verify_rows, dim3(1024), dim3(256), 0, s, rows, row_base, row_cap, d_res);
-  return hipGetLastError();
+// Two-pass index (SAM slabs; the general re-run; *_MODE=two): pass 1 (tile aggregates, their
+// exclusive scan, the slab aggregate) then k_index1 with every tile's incoming state.
+template <int F>
+hipError_t launch_two_pass(const SlabParams &p, DevResult *d_res, hipStream_t s, hipEvent_t ek0, hipEvent_t ek1) {
+  const dim3 g1(p.ntiles), block(NTHREADS);
+  if (ek0) (void)hipEventRecord(ek0, s);
+  hipLaunchKernelGGL(k_tile_agg<F>, g1, block, 0, s, p, p.tile_agg);
+  hipError_t e = scan_excl<typename Traits<F>::M>(p, p.tile_agg, (u64 *)p.tile_excl, 0, true, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_index1<F>, g1, block, 0, s, p);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (ek1) (void)hipEventRecord(ek1, s);
+  return finalize(p, F, d_res, s);
 }
 
 constexpr u32 FIX_GRID = 64;  // k_fixup workgroups: the queue is short on real data (a few items per 10 GiB)
 // The FASTQ tile pass: k_fq_tiles, the exclusive scan of the tile newline counts (and the
-// slab aggregate), k_fq_place, k_fixup, k_finalize.  index_ms (ek0 -> ek1) covers
-// k_fq_tiles alone.
-extern "C" hipError_t sidx_launch_fq_tiles(const SlabParams *pp, DevResult *d_res, hipStream_t s, hipEvent_t ek0,
-                                           hipEvent_t ek1) {
-  const SlabParams &p = *pp;
+// slab aggregate), k_fq_place, k_fixup (which finalizes the build).  index_ms (ek0 -> ek1)
+// covers k_fq_tiles alone, on the grid the caller sized for it (sidx_tiles_blocks_per_cu).
+hipError_t launch_fq(const SlabParams &p, DevResult *d_res, hipStream_t s, hipEvent_t ek0, hipEvent_t ek1) {
   // ek0 / ek1 time the tile pass alone: recorded by its dispatch packet (hipExtLaunchKernel),
   // not as separate stream packets that would add their own gaps to the build
   if (p.fq_lines) hipExtLaunchKernelGGL(k_fq_tiles<true>, dim3(p.pgrid), dim3(SNT), 0, s, ek0, ek1, 0, p);
   else hipExtLaunchKernelGGL(k_fq_tiles<false>, dim3(p.pgrid), dim3(SNT), 0, s, ek0, ek1, 0, p);
-  hipError_t e = scan_excl<CountMonoid>(p, p.fq_agg, (u64 *)p.tile_excl, 0, true, s, FQW_TMASK);
+  hipError_t e = scan_excl<CountMonoid>(p, p.tile_agg, (u64 *)p.tile_excl, 0, true, s, FQW_TMASK);
   if (e != hipSuccess) return e;
   // test hook (SHOCKIDX_DEBUG bit 12): fail after the scan, as a launch error there would --
   // the build's ticket / first-bad slot is then left unreset (tests/test_gpu_host.py)
   if (p.debug & 4096u) return hipErrorLaunchFailure;
-  const u64 pb = (p.ntiles + PLACE_TILES - 1) / PLACE_TILES;
-  hipLaunchKernelGGL(k_fq_place, dim3((u32)(pb < 65536 ? pb : 65536)), dim3(256), 0, s, p);
-  hipLaunchKernelGGL(k_fixup, dim3(FIX_GRID), dim3(256), 0, s, p, d_res);  // (finalizes the build)
+  hipLaunchKernelGGL(k_fq_place, dim3(place_grid(p.ntiles, PLACE_TILES)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(k_fixup, dim3(FIX_GRID), dim3(256), 0, s, p, d_res);
   return hipGetLastError();
+}
+
+// The FASTA tile pass: k_fa_tiles, the FastaMonoid scan of the tile aggregates, k_fa_place,
+// k_fa_fixup (which finalizes the build).
+hipError_t launch_fa(const SlabParams &p, DevResult *d_res, hipStream_t s, hipEvent_t ek0, hipEvent_t ek1) {
+  hipExtLaunchKernelGGL(k_fa_tiles, dim3(p.pgrid), dim3(SNT), 0, s, ek0, ek1, 0, p);
+  hipError_t e = scan_excl<FastaMonoid>(p, p.tile_agg, (u64 *)p.tile_excl, 0, true, s, FAW_AMASK);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_fa_place, dim3(place_grid(p.ntiles, PLACE_TILES)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(k_fa_fixup, dim3(FIX_GRID), dim3(256), 0, s, p, d_res);
+  return hipGetLastError();
+}
+
+// The line tile pass: k_line_tiles, the count scan (row bases, slab aggregate) and the max
+// scan of the last '\n' + 1 (each tile's first row start), k_line_place, k_line_final.
+hipError_t launch_line(const SlabParams &p, DevResult *d_res, hipStream_t s, hipEvent_t ek0, hipEvent_t ek1) {
+  hipExtLaunchKernelGGL(k_line_tiles, dim3(p.pgrid), dim3(SNT), 0, s, ek0, ek1, 0, p);
+  hipError_t e = scan_excl<CountMonoid>(p, p.tile_agg, (u64 *)p.tile_excl, 0, true, s, LCOUNT);
+  if (e == hipSuccess) e = scan_excl<MaxMonoid>(p, p.pcnt, p.ppre, 1, false, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_line_place<F_LINE>, dim3(place_grid(p.ntiles, LPLACE_TILES)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(k_line_final, dim3(1), dim3(64), 0, s, p);
+  return finalize(p, F_LINE, d_res, s);
+}
+
+// The SAM tile pass (single-slab builds): k_sam_tiles, the SamMonoid scan (incoming states,
+// the slab aggregate), k_sam_resolve, the max scan of the last terminator + 1, placement,
+// k_sam_final.
+hipError_t launch_sam(const SlabParams &p, DevResult *d_res, hipStream_t s, hipEvent_t ek0, hipEvent_t ek1) {
+  hipExtLaunchKernelGGL(k_sam_tiles, dim3(p.pgrid), dim3(SNT), 0, s, ek0, ek1, 0, p);
+  hipError_t e = scan_excl<SamMonoid>(p, p.tile_agg, (u64 *)p.tile_excl, 0, true, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_sam_resolve, dim3((p.ntiles + 255) / 256), dim3(256), 0, s, p);
+  e = scan_excl<MaxMonoid>(p, p.pcnt, p.ppre, 1, false, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_line_place<F_SAM>, dim3(place_grid(p.ntiles, LPLACE_TILES)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(k_sam_final, dim3(1), dim3(64), 0, s, p);
+  return finalize(p, F_SAM, d_res, s);
+}
+}  // namespace
+
+// One slab's build on the path the host chose (sidx_build.cpp choose_pass); the two-pass build
+// takes its format from the parameters (gate_fmt).  The FASTA, line and SAM tile kernels run on
+// their own persistent grid (tile_grid), FASTQ on the caller's.
+extern "C" hipError_t sidx_launch_tiles(TilePass pass, const SlabParams *pp, DevResult *d_res, hipStream_t s,
+                                        hipEvent_t ek0, hipEvent_t ek1) {
+  SlabParams p = *pp;
+  if (pass == TP_FA || pass == TP_LINE || pass == TP_SAM) p.pgrid = tile_grid(p, pass);
+  switch (pass) {
+    case TP_FQ: return launch_fq(p, d_res, s, ek0, ek1);
+    case TP_FA: return launch_fa(p, d_res, s, ek0, ek1);
+    case TP_LINE: return launch_line(p, d_res, s, ek0, ek1);
+    case TP_SAM: return launch_sam(p, d_res, s, ek0, ek1);
+    case TP_TWO_PASS:
+      switch (p.gate_fmt) {
+        case F_FASTQ: return launch_two_pass<F_FASTQ>(p, d_res, s, ek0, ek1);
+        case F_FASTA: return launch_two_pass<F_FASTA>(p, d_res, s, ek0, ek1);
+        case F_SAM: return launch_two_pass<F_SAM>(p, d_res, s, ek0, ek1);
+        case F_LINE: return launch_two_pass<F_LINE>(p, d_res, s, ek0, ek1);
+      }
+  }
+  return hipErrorInvalidValue;
+}
+
+// u32 words of SlabParams::tile_stage a tile pass needs.  Line / SAM: LCAP u16 '\n' positions per
+// tile.  FASTQ / FASTA: a slot of RCAP u32 per tile (FASTQ keeps FQ_LINE_E + FQ_OVF u16 starts in
+// it, FASTA RCAP u16 candidates), with the persistent grid + 16 tiles of slack that an earlier
+// layout needed (kept: the size feeds the device budget).
+static_assert(FQ_LINE_E + FQ_OVF <= 2 * RCAP, "a FASTQ tile's starts fit its slot");
+extern "C" u64 sidx_tile_stage_words(TilePass pass, u64 ntiles, u32 grid) {
+  return (pass == TP_LINE || pass == TP_SAM) ? ntiles * (LCAP / 2) : (ntiles + grid + 16) * (u64)RCAP;
 }
 
 extern "C" hipError_t sidx_launch_fq_spans_place(const SlabParams *pp, u32 *spans, u64 *outlen, u64 K, int kind,
                                                 hipStream_t s) {
   const SlabParams &p = *pp;
   if (!p.fq_lines || !p.ntiles) return hipSuccess;
-  const u64 wb = (p.ntiles + 3) / 4;
-  hipLaunchKernelGGL(k_fq_spans_place, dim3((u32)(wb < 65536 ? wb : 65536)), dim3(256), 0, s, p, spans, outlen, K, kind);
+  hipLaunchKernelGGL(k_fq_spans_place, dim3(place_grid(p.ntiles, 4)), dim3(256), 0, s, p, spans, outlen, K, kind);
   return hipGetLastError();
 }
 
-// The line tile pass: k_line_tiles, the count scan (row bases, slab aggregate) and the max
-// scan of the last '\n' + 1 (each tile's first row start), k_line_place, k_line_final.
-extern "C" hipError_t sidx_launch_line_tiles(const SlabParams *pp, DevResult *d_res, hipStream_t s, hipEvent_t ek0,
-                                             hipEvent_t ek1) {
-  const SlabParams &p = *pp;
-  SlabParams q = p;
-  q.pgrid = tile_grid(p, 2);
-  hipExtLaunchKernelGGL(k_line_tiles, dim3(q.pgrid), dim3(SNT), 0, s, ek0, ek1, 0, q);
-  hipError_t e = scan_excl<CountMonoid>(p, p.fq_agg, (u64 *)p.tile_excl, 0, true, s, LCOUNT);
-  if (e == hipSuccess) e = scan_excl<MaxMonoid>(p, p.pcnt, p.ppre, 1, false, s);
-  if (e != hipSuccess) return e;
-  const u64 wb = (p.ntiles + LPLACE_TILES - 1) / LPLACE_TILES;
-  hipLaunchKernelGGL(k_line_place<F_LINE>, dim3((u32)(wb < 65536 ? wb : 65536)), dim3(256), 0, s, p);
-  hipLaunchKernelGGL(k_line_final, dim3(1), dim3(64), 0, s, p);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, p, F_LINE, d_res);
-  return hipGetLastError();
-}
-
-// The SAM tile pass (single-slab builds): k_sam_tiles, the SamMonoid scan (incoming states,
-// the slab aggregate), k_sam_resolve, the max scan of the last terminator + 1, placement,
-// k_sam_final, k_finalize.
-extern "C" hipError_t sidx_launch_sam_tiles(const SlabParams *pp, DevResult *d_res, hipStream_t s, hipEvent_t ek0,
-                                            hipEvent_t ek1) {
-  const SlabParams &p = *pp;
-  SlabParams q = p;
-  q.pgrid = tile_grid(p, 3);
-  hipExtLaunchKernelGGL(k_sam_tiles, dim3(q.pgrid), dim3(SNT), 0, s, ek0, ek1, 0, q);
-  hipError_t e = scan_excl<SamMonoid>(p, p.fq_agg, (u64 *)p.tile_excl, 0, true, s);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_sam_resolve, dim3((p.ntiles + 255) / 256), dim3(256), 0, s, p);
-  e = scan_excl<MaxMonoid>(p, p.pcnt, p.ppre, 1, false, s);
-  if (e != hipSuccess) return e;
-  const u64 wb = (p.ntiles + LPLACE_TILES - 1) / LPLACE_TILES;
-  hipLaunchKernelGGL(k_line_place<F_SAM>, dim3((u32)(wb < 65536 ? wb : 65536)), dim3(256), 0, s, p);
-  hipLaunchKernelGGL(k_sam_final, dim3(1), dim3(64), 0, s, p);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, p, F_SAM, d_res);
-  return hipGetLastError();
-}
-
-// SHOCKIDX_SAM_MODE=two: the two-pass SAM build instead of the tile pass
-extern "C" int sidx_sam_tiles() {
-  const char *e = getenv("SHOCKIDX_SAM_MODE");
-  return (e && (!strcmp(e, "two") || !strcmp(e, "0"))) ? 0 : 1;
-}
-
-// SHOCKIDX_LINE_MODE=two: the two-pass line build instead of the tile pass
-extern "C" int sidx_line_tiles() {
-  const char *e = getenv("SHOCKIDX_LINE_MODE");
-  return (e && (!strcmp(e, "two") || !strcmp(e, "0"))) ? 0 : 1;
-}
-
-// The FASTA tile pass: k_fa_tiles, the FastaMonoid scan of the tile aggregates, k_fa_place,
-// k_fa_fixup, k_finalize.
-extern "C" hipError_t sidx_launch_fa_tiles(const SlabParams *pp, DevResult *d_res, hipStream_t s, hipEvent_t ek0,
-                                           hipEvent_t ek1) {
-  const SlabParams &p = *pp;
-  SlabParams q = p;
-  q.pgrid = tile_grid(p, 1);
-  hipExtLaunchKernelGGL(k_fa_tiles, dim3(q.pgrid), dim3(SNT), 0, s, ek0, ek1, 0, q);
-  hipError_t e = scan_excl<FastaMonoid>(p, p.fq_agg, (u64 *)p.tile_excl, 0, true, s, FAW_AMASK);
-  if (e != hipSuccess) return e;
-  const u64 pb = (p.ntiles + PLACE_TILES - 1) / PLACE_TILES;
-  hipLaunchKernelGGL(k_fa_place, dim3((u32)(pb < 65536 ? pb : 65536)), dim3(256), 0, s, p);
-  hipLaunchKernelGGL(k_fa_fixup, dim3(FIX_GRID), dim3(256), 0, s, p, d_res);  // (finalizes the build)
-  return hipGetLastError();
-}
-
-// SHOCKIDX_FA_MODE=two: the two-pass FASTA build (k_tile_agg + k_index1) instead of the tile pass
-// (read per build, so one process can compare both)
-extern "C" int sidx_fa_tiles() {
-  const char *e = getenv("SHOCKIDX_FA_MODE");
-  return (e && (!strcmp(e, "two") || !strcmp(e, "0"))) ? 0 : 1;
-}
-
-// Co-resident workgroups per CU of the tile passes (persistent grid = CUs x this).
-// 1: the FASTQ tile pass appends to per-XCD logs whose cursors the host zeroes before the pass
-
+// Co-resident workgroups per CU of the FASTQ tile pass (its persistent grid = CUs x this).
 extern "C" int sidx_tiles_blocks_per_cu() {
   int n = 0;
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_fq_tiles<false>, SNT, 0) == hipSuccess ? n : 0;

@@ -13,8 +13,11 @@
 extern "C" {
 
 hipError_t sidx_launch_detect(const uint8_t *d, sidx::u64 n, int *d_out, hipStream_t s);
-hipError_t sidx_launch_index(int fmt, const sidx::SlabParams *p, sidx::DevResult *d_res, hipStream_t s,
+// one slab's build on the given path (the two-pass build's format: p->gate_fmt)
+hipError_t sidx_launch_tiles(sidx::TilePass pass, const sidx::SlabParams *p, sidx::DevResult *d_res, hipStream_t s,
     hipEvent_t ek0, hipEvent_t ek1);
+// u32 words of SlabParams::tile_stage that path needs (grid: the caller's persistent grid)
+sidx::u64 sidx_tile_stage_words(sidx::TilePass pass, sidx::u64 ntiles, sidx::u32 grid);
 hipError_t sidx_launch_chunkrecord(const uint8_t *d, sidx::u64 n, int fasta, long long chunk, sidx::u64 *rows,
     sidx::u64 row_cap, sidx::u64 *out, long long curr0, sidx::u64 cnt0, sidx::u64 max_steps, hipStream_t s);
 hipError_t sidx_cr_gpos_count(const uint8_t *d, sidx::u64 n, sidx::u64 *tcnt, sidx::u64 *toff, uint16_t *slot,
@@ -73,17 +76,6 @@ hipError_t sidx_subset_runs(const sidx::u64 *rows, const sidx::u32 *startf, cons
     sidx::u64 *ctl, sidx::u64 *runs, sidx::u64 rows_cap, sidx::u64 runs_cap, hipStream_t s);
 hipError_t sidx_launch_fq_spans_place(const sidx::SlabParams *pp, sidx::u32 *spans, sidx::u64 *outlen, sidx::u64 K,
     int kind, hipStream_t s);
-hipError_t sidx_launch_fq_tiles(const sidx::SlabParams *pp, sidx::DevResult *d_res, hipStream_t s, hipEvent_t ek0,
-    hipEvent_t ek1);
-hipError_t sidx_launch_fa_tiles(const sidx::SlabParams *pp, sidx::DevResult *d_res, hipStream_t s, hipEvent_t ek0,
-    hipEvent_t ek1);
-int sidx_fa_tiles();
-hipError_t sidx_launch_line_tiles(const sidx::SlabParams *pp, sidx::DevResult *d_res, hipStream_t s, hipEvent_t ek0,
-    hipEvent_t ek1);
-int sidx_line_tiles();
-hipError_t sidx_launch_sam_tiles(const sidx::SlabParams *pp, sidx::DevResult *d_res, hipStream_t s, hipEvent_t ek0,
-    hipEvent_t ek1);
-int sidx_sam_tiles();
 hipError_t sidx_filter_spans(const uint8_t *data, sidx::u64 n, const sidx::u64 *rows, sidx::u64 K, int kind,
     sidx::u32 *spans, sidx::u64 *outlen, sidx::u64 *firstbad, hipStream_t s);
 hipError_t sidx_filter_write(const uint8_t *data, sidx::u64 n, const sidx::u64 *rows, const sidx::u32 *spans,
