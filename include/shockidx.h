@@ -23,6 +23,7 @@
  *   shockidx_chunkrecord_fd      the same over the node's *os.File (chunkrecord.go:43-56 reads it)
  *   shockidx_chunkrecord_subset_device  chunkRecord.Create for subset nodes (chunkrecord.go:100-228)
  *                          with fastq.go:216-243 / fasta.go:143-173 SeekChunk
+ *   shockidx_column_device / shockidx_column_fd  CreateColumnIndex: index/column.go:33-130
  *
  * Semantics: results are bit-identical to the Go path on the same bytes, including the
  * exact error strings (fastq.go:156-207, fasta.go:120, errors.go:20) and the record count
@@ -41,7 +42,9 @@ extern "C" {
 /* 5: shockidx_slab.seq, the summary's build tag and shockidx_slab_combine's expect_seq (a stale
  *    summary is refused); row-capacity errors of build_device / chunkrecord / subset are
  *    SHOCKIDX_ESPACE (4 returned SHOCKIDX_EINVAL); whole-file builds check their own table's
- *    end invariants (SHOCKIDX_EINTERNAL instead of a short table) */
+ *    end invariants (SHOCKIDX_EINTERNAL instead of a short table).
+ *    Added since without a version change (purely additive): shockidx_column_device,
+ *    shockidx_column_fd */
 #define SHOCKIDX_ABI_VERSION 5
 
 /* index kinds = the registry keys served (index/index.go:21-28) */
@@ -374,6 +377,32 @@ int shockidx_chunkrecord_fd(shockidx_ctx *ctx, int fd, uint64_t n, int fmt, uint
  * d_rows receives result->count rows (16 * first row, 16 * rows): the "matrix" index. */
 int shockidx_chunkrecord_subset_device(shockidx_ctx *ctx, const void *d_ri, uint64_t nrows, void *d_rows,
                                        uint64_t row_cap, shockidx_result *result);
+
+/* ---- column index ------------------------------------------------------------------------
+ * CreateColumnIndex (index/column.go:33-130, called from node/index.go:43-54 for
+ * PUT /node/{id}/index/column?number=N): a tab-separated file grouped by the runs of one
+ * column.  Lines are the ReadBytes('\n') pieces (column.go:54); a piece of at most one byte is
+ * skipped and its bytes stay with the open group (:64-72); a row ends before every other line
+ * whose column-th field (bytes.Split on '\t', :74-79; the last field keeps its "\n") differs
+ * from the previous compared line's (:80-98, prev_str starts ""), except at line 0.  Rows are
+ * contiguous (offset, length) pairs that cover the file; a file of one group has no rows
+ * (:119: curr == 0).  column counts from 1; column < 1 is SHOCKIDX_EINVAL (the controller
+ * rejects it, controller/node/index/index.go:218-228).
+ * Error: the first non-blank line with fewer than column fields returns SHOCKIDX_EFORMAT,
+ * "Specified column does not exist for all lines in file." (:75-77), count 0.  The reference
+ * tests len(slices) < column-1, so a line with exactly column-1 fields passes that test and
+ * panics at slices[column-1] (:79, index out of range: the server goes down); both cases
+ * return the error here.
+ * d_data: n bytes in HBM; d_rows: row_cap rows; a short row_cap returns SHOCKIDX_ESPACE with
+ * result->count = the rows needed.  result->format is SHOCKIDX_FMT_LINE; result->path is 1 for
+ * the tile pass (one read of the input) and 2 for the general build (the line index, then one key
+ * per line compared with its predecessor's; SHOCKIDX_COLUMN_MODE=two forces it). */
+int shockidx_column_device(shockidx_ctx *ctx, const void *d_data, uint64_t n, int column, void *d_rows,
+                           uint64_t row_cap, shockidx_result *result);
+/* The same over an open descriptor (not closed; pread from offset 0, short reads retried):
+ * *rows receives a malloc'ed table of result->count rows (free with shockidx_free). */
+int shockidx_column_fd(shockidx_ctx *ctx, int fd, uint64_t n, int column, uint64_t **rows,
+                       shockidx_result *result);
 
 void shockidx_free(void *p);
 const char *shockidx_strerror(int code);

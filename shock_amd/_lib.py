@@ -31,6 +31,7 @@ EXPORTS = ("shockidx_ctx_create", "shockidx_ctx_destroy", "shockidx_build_device
            "shockidx_comm_allgather", "shockidx_comm_destroy", "shockidx_comm_count", "shockidx_subset_index", "shockidx_subset_gather",
            "shockidx_subset_node",
            "shockidx_chunkrecord_device", "shockidx_chunkrecord_fd", "shockidx_chunkrecord_subset_device", "shockidx_create_subset_index",
+           "shockidx_column_device", "shockidx_column_fd",
            "shockidx_idx_part", "shockidx_idx_range", "shockidx_filter_device", "shockidx_ctx_trim",
            "shockidx_ctx_workspace_bytes", "shockidx_ctx_set_dev_cap", "shockidx_multi_create", "shockidx_multi_destroy", "shockidx_multi_rccl",
            "shockidx_multi_build_host", "shockidx_multi_build_fd", "shockidx_multi_create_index", "shockidx_multi_plan",
@@ -118,6 +119,10 @@ def lib():
     L.shockidx_chunkrecord_fd.restype = i32
     L.shockidx_chunkrecord_subset_device.argtypes = [vp, vp, u64, vp, u64, PRes]
     L.shockidx_chunkrecord_subset_device.restype = i32
+    L.shockidx_column_device.argtypes = [vp, vp, u64, i32, vp, u64, PRes]
+    L.shockidx_column_device.restype = i32
+    L.shockidx_column_fd.argtypes = [vp, i32, u64, i32, PPu64, PRes]
+    L.shockidx_column_fd.restype = i32
     L.shockidx_build_host.argtypes = [vp, vp, u64, i32, i32, PPu64, PRes]
     L.shockidx_build_host.restype = i32
     L.shockidx_host_register.argtypes = [vp, vp, u64]

@@ -204,6 +204,47 @@ class Context:
         """Rows a chunkrecord build can produce (include/shockidx.h)."""
         return n // ((chunk or 1048576) - 32767) + 2
 
+    # -- column index (index/column.go:33-130) ---------------------------------------------------
+    def column_device(self, d_data: int, n: int, column: int, d_rows: int, row_cap: int) -> IndexResult:
+        """CreateColumnIndex over device memory: rows of the runs of the column-th tab-separated
+        field (column counts from 1).  EFORMAT carries Go's "Specified column does not exist ..."."""
+        res = L.Result()
+        rc = self._lib.shockidx_column_device(self._h, d_data, n, column, d_rows, row_cap, ctypes.byref(res))
+        return _result(res, rc)
+
+    def column_buffer(self, data: "DeviceBuffer", n: int, column: int, rows: "DeviceBuffer") -> IndexResult:
+        return self.column_device(data.ptr, n, column, rows.ptr, rows.nbytes // 16)
+
+    def column_fd(self, fd: int, size: int, column: int) -> IndexResult:
+        """CreateColumnIndex over an open file (shockidx_column_fd); rows on the host."""
+        res = L.Result()
+        rows_p = ctypes.POINTER(ctypes.c_uint64)()
+        rc = self._lib.shockidx_column_fd(self._h, fd, size, column, ctypes.byref(rows_p), ctypes.byref(res))
+        rows = _take_rows(rows_p, int(res.count)) if rows_p else None
+        return _result(res, rc, rows)
+
+    def column_host(self, data, column: int) -> IndexResult:
+        """Host-memory convenience: upload, build on the device, download the rows."""
+        data = bytes(data)
+        n = len(data)
+        d_in = self.alloc(n + 64)
+        d_in.upload(data)
+        cap = 1024
+        d_rows = self.alloc(16 * cap)
+        try:
+            r = self.column_buffer(d_in, n, column, d_rows)
+            if r.status == L.ESPACE:  # r.count holds the rows needed
+                d_rows.free()
+                cap = r.count
+                d_rows = self.alloc(16 * cap)
+                r = self.column_buffer(d_in, n, column, d_rows)
+            if r.status == L.OK:
+                r.rows = d_rows.rows(r.count) if r.count else np.zeros((0, 2), np.uint64)
+            return r
+        finally:
+            d_in.free()
+            d_rows.free()
+
     def set_dev_cap(self, nbytes: int) -> None:
         """Device bytes one fd build may hold (shockidx_ctx_set_dev_cap; 0: what is free).  A node
         whose one-pass build would not fit is indexed through two slab slots sized to the cap."""

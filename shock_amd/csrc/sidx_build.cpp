@@ -95,7 +95,7 @@ int set_msg(shockidx_result *r, int code, const char *msg) {
   return code;
 }
 
-static bool verify_rows() {
+bool verify_rows() {
   const char *v = getenv("SHOCKIDX_VERIFY");
   return v && *v && strcmp(v, "0") != 0;
 }
@@ -121,7 +121,7 @@ int ensure_dev(shockidx_ctx *c, void **p, u64 *cap, u64 need, size_t elem, shock
 u64 workspace_bytes(const shockidx_ctx *c) {
   // (13 undercounts the per-tile words: ensure_tiles holds STATUS_ARRAYS + 4 detail + 4 fix = 15; to be fixed)
   return c->d_in_cap + 16 * c->d_rows_cap + 13 * 8 * c->tiles_cap + c->d_sub_cap +
-         4 * (c->tile_stage_cap + c->tile_words_cap) + 2 * c->fqlines_cap + c->cra_cap + c->crb_cap + 2 * c->slot_cap;
+         4 * (c->tile_stage_cap + c->tile_words_cap) + 2 * c->fqlines_cap + c->cra_cap + c->crb_cap + 2 * c->slot_cap + c->cola_cap + c->colb_cap;
 }
 
 // free the large caches (they regrow on demand); the tile status words go only with keep = 0
@@ -142,6 +142,8 @@ void trim_workspace(shockidx_ctx *c, u64 keep) {
   c->last_spans = false;
   drop((void *&)c->d_cra, c->cra_cap);
   drop((void *&)c->d_crb, c->crb_cap);
+  drop((void *&)c->d_cola, c->cola_cap);
+  drop((void *&)c->d_colb, c->colb_cap);
   for (int i = 0; i < 2; ++i) {
     if (c->d_slot[i]) (void)hipFree(c->d_slot[i]);
     c->d_slot[i] = nullptr;

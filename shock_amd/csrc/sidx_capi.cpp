@@ -180,6 +180,8 @@ void shockidx_ctx_destroy(shockidx_ctx *c) {
   (void)hipFree(c->d_fqlines);
   (void)hipFree(c->d_cra);
   (void)hipFree(c->d_crb);
+  (void)hipFree(c->d_cola);
+  (void)hipFree(c->d_colb);
   for (int i = 0; i < 2; ++i) (void)hipFree(c->d_slot[i]);
   delete c->pool;
   if (c->ev0) (void)hipEventDestroy(c->ev0);

@@ -164,6 +164,13 @@ constexpr u32 RF_HALO = 4;       // the slab's halo ended before a record could 
 constexpr u32 RF_FIXQUEUE = 8;   // the k_fixup queue overflowed: the host re-runs the two-pass build
 constexpr u32 RF_MISSPEC = 16;   // gated build: k_detect found another format than the speculated one
 
+// Column index (sidx_column.hip): a non-blank line's start and its key span, and the build's
+// control words (the first line without the column, the non-blank lines, the cuts).
+struct ColKey {
+  u64 off, lo, len;
+};
+enum ColCtl : int { COL_BAD = 0, COL_NB, COL_B, COL_CTL_WORDS };
+
 // Device result of finalize (mirrored by shockidx_result in include/shockidx.h).
 struct DevResult {
   u64 count;       // records (rows) produced, Go's `count`

@@ -100,6 +100,10 @@ struct shockidx_ctx {
   u64 slot_cap = 0;                //   (bytes each)
   u64 crb_cap = 0;
   u32 cr_grid = 0;                 //   k_cr_verify persistent grid
+  uint8_t *d_cola = nullptr;       // column index: the line table, then the cut offsets (bytes)
+  u64 cola_cap = 0;
+  uint8_t *d_colb = nullptr;       //   flags, ranks, key spans, scan workspace (bytes)
+  u64 colb_cap = 0;
   hipStream_t s_copy = nullptr;    // slab-pipelined host builds: the H2D stream
   uint8_t *h_rows[2] = {nullptr, nullptr};  // slab-pipelined fd builds: pinned row staging (D2H)
   // download filters over FASTQ: the tile pass keeps each record's line ends (k_fq_tiles<true>)
@@ -219,6 +223,8 @@ int respeculate(shockidx_ctx *c, const sidx::DevResult &dr, int *kfmt, shockidx_
 int run_index(shockidx_ctx *c, const uint8_t *d_data, sidx::u64 n, int kfmt, sidx::u64 *d_rows, sidx::u64 row_cap,
               hipStream_t s, sidx::DevResult *dr, shockidx_result *res, const SlabGeom *geom = nullptr,
               bool general = false, const int *gate = nullptr);
+// SHOCKIDX_VERIFY is set (and not "0"): builds check their finished table on the device
+bool verify_rows();
 int translate(shockidx_ctx *c, const sidx::DevResult &dr, const uint8_t *d_data, hipStream_t s, shockidx_result *res);
 int build_resident(shockidx_ctx *c, const uint8_t *d_data, sidx::u64 n, int kind, int fmt, hipStream_t s,
                    shockidx_result *res);

@@ -65,6 +65,23 @@ hipError_t sidx_scan_flags(const sidx::u32 *in, sidx::u64 *out, sidx::u64 n, voi
     hipStream_t s);
 hipError_t sidx_scan_u64(const sidx::u64 *in, sidx::u64 *out, sidx::u64 n, void *tmp, size_t *tmp_bytes,
     hipStream_t s);
+// column index (sidx_column.hip): the scans' temp bytes for L lines; the build up to the cut
+// offsets (written over the line table lt); the rows from them; the SHOCKIDX_VERIFY end check
+sidx::u64 sidx_col_scan_bytes(sidx::u64 L);
+hipError_t sidx_col_cuts(const uint8_t *d, sidx::u64 n, sidx::u64 *lt, sidx::u64 L, sidx::u32 column,
+    sidx::u32 *flag, sidx::u64 *rank, sidx::ColKey *ck, sidx::u64 *ctl, void *scan_tmp, size_t scan_bytes,
+    hipStream_t s);
+hipError_t sidx_col_rows(const sidx::u64 *cuts, const sidx::u64 *ctl, sidx::u64 B, sidx::u64 n, sidx::u64 *rows,
+    sidx::u64 row_cap, hipStream_t s);
+// the tile pass: its workspace bytes; up to the cut count (*ctl: the control words inside ws);
+// the count rows from the workspace
+sidx::u64 sidx_col_tile_bytes(sidx::u64 ntiles);
+hipError_t sidx_col_tile_cuts(const uint8_t *d, sidx::u64 n, sidx::u32 column, sidx::u32 grid, void *ws,
+    const sidx::u64 **ctl, hipStream_t s);
+hipError_t sidx_col_tile_rows(sidx::u64 n, void *ws, sidx::u64 count, sidx::u64 *rows, sidx::u64 row_cap,
+    hipStream_t s);
+hipError_t sidx_col_check(const sidx::u64 *rows, sidx::u64 count, sidx::u64 n, sidx::DevResult *d_res,
+    hipStream_t s);
 hipError_t sidx_subset_compact(const sidx::u32 *keep, const sidx::u64 *rank, const sidx::i64 *val,
     const sidx::u32 *st, sidx::u64 m, sidx::i64 *cval, sidx::u32 *cst, sidx::u64 *cline, sidx::u64 *ctl,
     hipStream_t s);

@@ -131,6 +131,41 @@ def NewLineIndexer(f, n_type="", sn_format="", sn_index_path=""):  # noqa: N802
     return LineIndexer(f, n_type, sn_format, sn_index_path)
 
 
+class ColumnIndexer:
+    """index/column.go:15-31: the column indexer holds the file; its own Create is a stub
+    (:29-31) and CreateColumnIndex does the work."""
+
+    def __init__(self, f):
+        self.f = f
+
+    def create(self, file: str = ""):
+        return 0, "", None
+
+    def close(self):
+        self.f.close()
+
+
+def NewColumnIndexer(f):  # noqa: N802 (column.go:21)
+    return ColumnIndexer(f)
+
+
+def CreateColumnIndex(c: ColumnIndexer, column: int, ofile: str):  # noqa: N802 (column.go:33-130)
+    """-> (count, "array", err).  The table goes to <PATH_DATA>/temp and is renamed to ofile
+    (a zero-byte file for a single group, as the reference); on the missing-column error nothing is
+    written to ofile.  node/index.go:50-51 calls this directly: "column" is not in Indexers."""
+    fd = c.f.fileno()
+    size = os.fstat(fd).st_size
+    r = context().column_fd(fd, size, int(column))
+    if r.status == L.EFORMAT:
+        return 0, "array", ShockIndexError(r.err)
+    if r.status != L.OK:
+        raise L.ShockIdxError(r.status, (r.err or b"").decode("utf-8", "replace"))
+    tmpdir = os.path.join(PATH_DATA, "temp")
+    os.makedirs(tmpdir, exist_ok=True)
+    write_idx(r.rows if r.rows is not None else np.zeros((0, 2), np.uint64), tmpdir, ofile)
+    return r.count, "array", None
+
+
 # index.go:21-28 -- the GPU path serves the scanning indexers; "size" (no scan) is not provided.
 Indexers = {
     "chunkrecord": NewChunkRecordIndexer,
