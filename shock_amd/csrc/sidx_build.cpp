@@ -77,22 +77,8 @@ void CopyPool::run(int i) {
 
 constexpr u64 SPEC_MIN_BYTES = 1ull << 20;  // smaller AUTO builds detect first (a re-run costs little)
 
-int set_hip(shockidx_result *r, hipError_t e, const char *what) {
-  if (r) {
-    snprintf(r->err, sizeof r->err, "%s: %s", what, hipGetErrorString(e));
-    r->err_len = strlen(r->err);
-    r->status = SHOCKIDX_EHIP;
-  }
-  return SHOCKIDX_EHIP;
-}
-
-int set_msg(shockidx_result *r, int code, const char *msg) {
-  if (r) {
-    snprintf(r->err, sizeof r->err, "%s", msg);
-    r->err_len = strlen(r->err);
-    r->status = code;
-  }
-  return code;
+int set_hip(Err r, hipError_t e, const char *what) {
+  return set_msg(r, SHOCKIDX_EHIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
 bool verify_rows() {
@@ -106,91 +92,48 @@ static bool ws_contig(int bit) {
   const char *e = getenv("SHOCKIDX_CONTIG_WS");
   return e && (atoi(e) & bit);
 }
-int ensure_dev(shockidx_ctx *c, void **p, u64 *cap, u64 need, size_t elem, shockidx_result *res, bool node) {
-  if (*cap >= need && *p) return 0;
-  if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-  u64 want = need + need / 8 + 64;
-  HIPCHK(dev_malloc(p, want * elem + 64, node), "hipMalloc");
-  *cap = want;
-  (void)c;
-  return 0;
-}
 
-// device bytes held by the context's grow-only caches (input staging, rows, tile status,
-// scan and subset workspaces)
-u64 workspace_bytes(const shockidx_ctx *c) {
-  // (13 undercounts the per-tile words: ensure_tiles holds STATUS_ARRAYS + 4 detail + 4 fix = 15; to be fixed)
-  return c->d_in_cap + 16 * c->d_rows_cap + 13 * 8 * c->tiles_cap + c->d_sub_cap +
-         4 * (c->tile_stage_cap + c->tile_words_cap) + 2 * c->fqlines_cap + c->cra_cap + c->crb_cap + 2 * c->slot_cap + c->cola_cap + c->colb_cap;
-}
-
-// free the large caches (they regrow on demand); the tile status words go only with keep = 0
+// free the large caches (they regrow on demand); the tile block goes only with keep = 0, or when
+// the rest is still over keep
 void trim_workspace(shockidx_ctx *c, u64 keep) {
-  if (workspace_bytes(c) <= keep) return;
-  (void)hipStreamSynchronize(c->stream);
-  auto drop = [](void *&p, auto &cap) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  };
-  drop((void *&)c->d_in, c->d_in_cap);
-  drop((void *&)c->d_rows, c->d_rows_cap);
-  drop((void *&)c->d_sub, c->d_sub_cap);
-  drop((void *&)c->d_tile_stage, c->tile_stage_cap);
-  drop((void *&)c->d_tile_words, c->tile_words_cap);
-  drop((void *&)c->d_fqlines, c->fqlines_cap);
-  c->last_spans = false;
-  drop((void *&)c->d_cra, c->cra_cap);
-  drop((void *&)c->d_crb, c->crb_cap);
-  drop((void *&)c->d_cola, c->cola_cap);
-  drop((void *&)c->d_colb, c->colb_cap);
-  for (int i = 0; i < 2; ++i) {
-    if (c->d_slot[i]) (void)hipFree(c->d_slot[i]);
-    c->d_slot[i] = nullptr;
-  }
-  c->slot_cap = 0;
-  if (keep == 0 || workspace_bytes(c) > keep) {
-    (void)hipFree(c->d_status);
-    (void)hipFree(c->d_detail);
-    (void)hipFree(c->d_fix);
-    c->d_status = c->d_detail = c->d_fix = nullptr;
-    c->tiles_cap = 0;  // a fresh (zeroed) status array comes back with the next build
-  }
+  if (c->bufs.trim(keep, [c] { (void)hipStreamSynchronize(c->stream); })) c->last_spans = false;
 }
 
 // test hook: every status word published (INC) with the next build's epoch and payload 0, on
 // the build stream -- the stale look-back words a recycled allocation could hold
-static hipError_t poison_status(shockidx_ctx *c, u64 tiles_cap) {
+static hipError_t poison_status(shockidx_ctx *c) {
   const u64 w = FLAG_INC | ((u64)((c->epoch + 1) & EPOCH_MASK) << EPOCH_SHIFT);
-  std::vector<u64> h(STATUS_ARRAYS * tiles_cap, w);
+  std::vector<u64> h(c->d_status.cap, w);
   hipError_t e = hipMemcpyAsync(c->d_status, h.data(), h.size() * sizeof(u64), hipMemcpyHostToDevice, c->stream);
   return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
 }
 
-static int ensure_tiles(shockidx_ctx *c, u64 ntiles, shockidx_result *res) {
-  if (c->tiles_cap >= ntiles && c->d_status) return 0;
+// The tile block for ntiles tiles: the three buffers grow together (c->tiles_cap() tiles), and a
+// build never sees a part of it -- whatever fails, the whole block is dropped.
+static int ensure_tiles(shockidx_ctx *c, u64 ntiles, Err res) {
+  if (c->tiles_cap() >= ntiles && c->d_status) return 0;
   // the fresh array is zeroed, so any epoch >= 1 is unpublished; the epoch keeps counting so
   // the first-bad / counter slots keep alternating (finalize resets the next build's slot)
-  if (c->d_status) (void)hipFree(c->d_status);
-  if (c->d_detail) (void)hipFree(c->d_detail);
-  if (c->d_fix) (void)hipFree(c->d_fix);
-  c->d_fix = nullptr;
-  c->d_status = nullptr;
-  c->d_detail = nullptr;
-  u64 want = ntiles + ntiles / 8 + 64;
-  // the status block: STATUS_ARRAYS words per tile (StatusArray, sidx_host.hpp)
-  HIPCHK(dev_malloc((void **)&c->d_status, STATUS_ARRAYS * want * sizeof(u64), ws_contig(1)), "hipMalloc(status)");
-  // detail slots: one per tile (+1) and one per k_fixup queue item (the FASTA tile pass)
-  HIPCHK(hipMalloc((void **)&c->d_detail, 4 * want * sizeof(u64)), "hipMalloc(detail)");
-  HIPCHK(hipMalloc((void **)&c->d_fix, 4 * want * sizeof(u64)), "hipMalloc(fix)");
-  // on the build stream and waited for: a null-stream memset is not ordered with the
-  // non-blocking context stream, and a reused allocation's old look-back words could be read
-  if (c->inject & 1) HIPCHK(poison_status(c, want), "poison");
-  HIPCHK(hipMemsetAsync(c->d_status, 0, STATUS_ARRAYS * want * sizeof(u64), c->stream), "hipMemset(status)");
-  if (c->inject & 2) HIPCHK(poison_status(c, want), "poison");
-  HIPCHK(hipStreamSynchronize(c->stream), "hipMemset(status) sync");
-  c->tiles_cap = want;
-  return 0;
+  c->bufs.drop(BufClass::Tile);
+  const u64 want = ntiles + ntiles / 8 + 64;
+  auto fresh = [&]() -> int {
+    // the status block: STATUS_ARRAYS words per tile (StatusArray, sidx_host.hpp)
+    c->d_status.node = ws_contig(1);
+    if (int rc = c->d_status.exact(STATUS_ARRAYS * want, res)) return rc;
+    // detail slots: one per tile (+1) and one per k_fixup queue item (the FASTA tile pass)
+    if (int rc = c->d_detail.exact(4 * want, res)) return rc;
+    if (int rc = c->d_fix.exact(4 * want, res)) return rc;
+    // on the build stream and waited for: a null-stream memset is not ordered with the
+    // non-blocking context stream, and a reused allocation's old look-back words could be read
+    if (c->inject & 1) HIPCHK(poison_status(c), "poison");
+    HIPCHK(hipMemsetAsync(c->d_status, 0, c->d_status.bytes(), c->stream), "hipMemset(status)");
+    if (c->inject & 2) HIPCHK(poison_status(c), "poison");
+    HIPCHK(hipStreamSynchronize(c->stream), "hipMemset(status) sync");
+    return 0;
+  };
+  const int rc = fresh();
+  if (rc) c->bufs.drop(BufClass::Tile);
+  return rc;
 }
 
 // resolve kind/fmt into the kernel format (device detection when AUTO).  With `gate`, an AUTO
@@ -198,7 +141,7 @@ static int ensure_tiles(shockidx_ctx *c, u64 ntiles, shockidx_result *res) {
 // k_detect is launched without waiting for it, *gate points at its result and the pipeline's
 // kernels run only if it matches (SlabParams::gate); one host round trip per build instead of two.
 int resolve_format(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kind, int fmt, hipStream_t s,
-                   int *kfmt, shockidx_result *res, const int **gate) {
+                   int *kfmt, Err res, const int **gate) {
   if (gate) *gate = nullptr;
   if (kind == SHOCKIDX_LINE) { *kfmt = F_LINE; return 0; }
   if (kind != SHOCKIDX_RECORD) return set_msg(res, SHOCKIDX_EINVAL, "invalid index kind");
@@ -271,7 +214,7 @@ static bool forced_two_pass(const char *envname) {
 static TilePass choose_pass(const shockidx_ctx *c, int kfmt, u64 n, const SlabGeom *geom, bool general) {
   if (general || !c->d_fix) return TP_TWO_PASS;  // (no k_fixup queue: k_index1 for every format)
   if (kfmt == F_FASTQ) return TP_FQ;
-  const bool fa_key_fits = 2 * c->tiles_cap < (1ull << KEY_TILE_BITS);
+  const bool fa_key_fits = 2 * c->tiles_cap() < (1ull << KEY_TILE_BITS);
   if (kfmt == F_FASTA && (!geom || n > 0) && !forced_two_pass("SHOCKIDX_FA_MODE") && fa_key_fits) return TP_FA;
   if (kfmt == F_LINE && n > 0 && !forced_two_pass("SHOCKIDX_LINE_MODE")) return TP_LINE;
   if (kfmt == F_SAM && n > 0 && !geom && !forced_two_pass("SHOCKIDX_SAM_MODE")) return TP_SAM;
@@ -288,13 +231,14 @@ int run_index(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kfmt, u64 *d_ro
   const TilePass pass = choose_pass(c, kfmt, n, geom, general);
   if (pass != TP_TWO_PASS) {  // the tile pass's staged positions and per-tile results
     const u64 words = sidx_tile_stage_words(pass, ntiles, c->tiles_grid);
-    if (int rc = ensure_dev(c, (void **)&c->d_tile_stage, &c->tile_stage_cap, words, 4, res, ws_contig(2))) return rc;
-    if (int rc = ensure_dev(c, (void **)&c->d_tile_words, &c->tile_words_cap, ntiles * FQ_TILE_WORDS, 4, res)) return rc;
+    c->d_tile_stage.node = ws_contig(2);
+    if (int rc = c->d_tile_stage.ensure(words, res)) return rc;
+    if (int rc = c->d_tile_words.ensure(ntiles * FQ_TILE_WORDS, res)) return rc;
     if (pass == TP_FQ && c->want_spans)
-      if (int rc = ensure_dev(c, (void **)&c->d_fqlines, &c->fqlines_cap, ntiles * 3 * (TILE / 64), 2, res)) return rc;
+      if (int rc = c->d_fqlines.ensure(ntiles * 3 * (TILE / 64), res)) return rc;
   }
   if (getenv("SHOCKIDX_TIMING") && !c->d_timing) {
-    HIPCHK(hipMalloc((void **)&c->d_timing, 9 * 8 * 65536), "hipMalloc(timing)");
+    HIPCHK(hipMalloc(&c->d_timing, 9 * 8 * 65536), "hipMalloc(timing)");
   }
   // A build that stopped between taking its epoch and its finalize (a launch or sync error)
   // left its first-bad / counter slot, scan tickets included, unreset: reset both slots before
@@ -307,7 +251,7 @@ int run_index(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kfmt, u64 *d_ro
   // next epoch (taken only once every allocation above succeeded); when the 14-bit epoch wraps,
   // clear the status array so no stale word can carry the current epoch
   if (++c->epoch > EPOCH_MASK) {
-    HIPCHK(hipMemsetAsync(c->d_status, 0, STATUS_ARRAYS * c->tiles_cap * sizeof(u64), s), "status clear");
+    HIPCHK(hipMemsetAsync(c->d_status, 0, c->d_status.bytes(), s), "status clear");
     c->epoch = 2;  // keep the slot parity alternating across the wrap (EPOCH_MASK is odd)
   }
   c->slots_dirty = true;  // until this build's finalize has run (the sync below)
@@ -324,7 +268,7 @@ int run_index(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kfmt, u64 *d_ro
   p.summary = geom ? (u64 *)geom->d_summary : nullptr;
   p.row_cap = row_cap;
   p.rows = d_rows;
-  auto status_array = [c](StatusArray a) { return c->d_status + (u64)a * c->tiles_cap; };
+  auto status_array = [c](StatusArray a) { return c->d_status + (u64)a * c->tiles_cap(); };
   p.status = status_array(SA_STATUS);
   p.pcnt = status_array(SA_PCNT);
   p.ppre = status_array(SA_PPRE);
@@ -332,8 +276,8 @@ int run_index(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kfmt, u64 *d_ro
   p.tile_agg = status_array(SA_TILE_AGG);
   p.tile_excl = status_array(SA_TILE_EXCL);
   p.pgrid = c->tiles_grid < ntiles ? c->tiles_grid : (u32)ntiles;
-  p.fix = general ? nullptr : c->d_fix;  // null: the two-pass build (k_index1) for every format
-  p.fixcap = (u32)c->tiles_cap;
+  p.fix = general ? nullptr : c->d_fix.get();  // null: the two-pass build (k_index1) for every format
+  p.fixcap = (u32)c->tiles_cap();
   p.badkey = (u64 *)(c->d_small + SMALL_BADKEY + 8 * slot);
   p.badkey_next = (u64 *)(c->d_small + SMALL_BADKEY + 8 * (slot ^ 1));
   p.detail = c->d_detail;
@@ -358,7 +302,7 @@ int run_index(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kfmt, u64 *d_ro
     p.tile_stage = c->d_tile_stage;
     p.tile_words = c->d_tile_words;
   }
-  p.fq_lines = (pass == TP_FQ && c->want_spans) ? c->d_fqlines : nullptr;
+  p.fq_lines = (pass == TP_FQ && c->want_spans) ? c->d_fqlines.get() : nullptr;
   c->last_spans = false;
   // One build's device work at a time per GPU: each build alone saturates HBM, so builds
   // from different contexts (concurrent goroutines, §8(b) "Threading") run back to back
@@ -437,9 +381,9 @@ int build_resident(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kind, int 
   res->format = kfmt == F_LINE ? SHOCKIDX_FMT_LINE : kfmt;
   u64 cap = kfmt == F_LINE ? n / 16 + 4096 : n / 32 + 4096;
   for (int attempt = 0; attempt < 3; ++attempt) {
-    if (int rc = ensure_dev(c, (void **)&c->d_rows, &c->d_rows_cap, cap, 16, res)) return rc;
+    if (int rc = c->d_rows.ensure(cap, res)) return rc;
     DevResult dr;
-    if (int rc = run_index(c, d_data, n, kfmt, c->d_rows, c->d_rows_cap, s, &dr, res, nullptr, false, gate)) return rc;
+    if (int rc = run_index(c, d_data, n, kfmt, c->d_rows, c->d_rows.cap, s, &dr, res, nullptr, false, gate)) return rc;
     if (gate) {
       gate = nullptr;
       if (int rc = respeculate(c, dr, &kfmt, res)) {
@@ -473,7 +417,7 @@ uint64_t *alloc_rows_out(size_t bytes) {
 // Device rows -> host memory through the pinned staging: the DMA of chunk i + 1 overlaps the
 // (threaded) host copy of chunk i.
 int rows_to_host(shockidx_ctx *c, const u64 *d_src, size_t bytes, uint8_t *dst, hipStream_t s,
-                 shockidx_result *res) {
+                 Err res) {
   size_t issued = 0, done = 0;
   int i = 0;
   auto issue = [&](int b) -> hipError_t {
@@ -516,7 +460,7 @@ int fetch_rows(shockidx_ctx *c, u64 count, hipStream_t s, uint64_t **rows, shock
 template <class Fill>
 static int stage_in(shockidx_ctx *c, u64 n, hipStream_t s, Fill fill, shockidx_result *res, u64 from = 0) {
   const double t0 = now_ms();
-  if (int rc = ensure_dev(c, (void **)&c->d_in, &c->d_in_cap, n + 64, 1, res, true)) return rc;
+  if (int rc = c->d_in.ensure(n + 64, res)) return rc;
   u64 off = from;
   int i = 0;
   while (off < n) {
@@ -614,7 +558,7 @@ void pin_release(u64 b) { g_pinned.fetch_sub(b); }
 int stage_fd(shockidx_ctx *c, int fd, u64 off, u64 n, hipStream_t s, shockidx_result *res) {
   u64 done = 0;
   if (n >= (64ull << 20) && !getenv("SHOCKIDX_NO_MMAP_DMA")) {
-    if (int rc = ensure_dev(c, (void **)&c->d_in, &c->d_in_cap, n + 64, 1, res, true)) return rc;
+    if (int rc = c->d_in.ensure(n + 64, res)) return rc;
     const double t0 = now_ms();
     const u64 a0 = off & ~4095ull, lead = off - a0;
     const size_t maplen = (size_t)(((off + n + 4095) & ~4095ull) - a0);
@@ -667,7 +611,7 @@ u64 dev_budget(shockidx_ctx *c) {
   }
   return c->dev_cap && c->dev_cap < avail ? c->dev_cap : avail;
 }
-// what a one-pass build of an n-byte node holds at its peak: the node, its rows (ensure_dev's
+// what a one-pass build of an n-byte node holds at its peak: the node, its rows (DevBuf::ensure's
 // growth included) and the per-tile workspaces
 u64 one_pass_bytes(u64 n) { return n + n / 8 + (n / 32) * 16 * 9 / 8 + n / 8 + (64ull << 20); }
 
@@ -679,16 +623,12 @@ hipError_t dev_malloc(void **p, size_t bytes, bool node) {
   return hipMalloc(p, bytes);
 }
 
-int sub_msg(shockidx_subset_result *r, int code, const std::string &m) {
-  const size_t k = m.size() < sizeof r->err - 1 ? m.size() : sizeof r->err - 1;
-  memcpy(r->err, m.data(), k);
-  r->err[k] = 0;
-  r->err_len = k;
-  r->status = code;
-  return code;
-}
-int sub_hip(shockidx_subset_result *r, hipError_t e, const char *what) {
-  return sub_msg(r, SHOCKIDX_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+static int hip_alloc(void **p, size_t bytes, bool node) { return (int)dev_malloc(p, bytes, node); }
+static void hip_release(void *p) { (void)hipFree(p); }
+static const char *hip_errstr(int e) { return hipGetErrorString((hipError_t)e); }
+const DevAlloc *hip_allocator() {
+  static const DevAlloc a = {hip_alloc, hip_release, hip_errstr};
+  return &a;
 }
 
 }  // namespace sidx_host

@@ -75,7 +75,7 @@ const char *shockidx_strerror(int code) {
 void shockidx_free(void *p) { free(p); }
 
 int shockidx_host_register(shockidx_ctx *c, void *p, uint64_t n) {
-  shockidx_result tmp, *res = &tmp;
+  const Err res;  // (the text is discarded: the code is what the caller gets)
   if (!c || !p || !n) return SHOCKIDX_EINVAL;
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   HIPCHK(hipHostRegister(p, n, hipHostRegisterDefault), "hipHostRegister");
@@ -83,7 +83,7 @@ int shockidx_host_register(shockidx_ctx *c, void *p, uint64_t n) {
 }
 
 int shockidx_host_unregister(shockidx_ctx *c, void *p) {
-  shockidx_result tmp, *res = &tmp;
+  const Err res;  // (the text is discarded: the code is what the caller gets)
   if (!c || !p) return SHOCKIDX_EINVAL;
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   HIPCHK(hipHostUnregister(p), "hipHostUnregister");
@@ -91,9 +91,7 @@ int shockidx_host_unregister(shockidx_ctx *c, void *p) {
 }
 
 int shockidx_ctx_create(int device, shockidx_ctx **out) {
-  shockidx_result tmp;
-  shockidx_result *res = &tmp;
-  reset_result(res);
+  const Err res;  // (the text is discarded: the code is what the caller gets)
   if (!out) return SHOCKIDX_EINVAL;
   *out = nullptr;
   int ndev = 0;
@@ -108,7 +106,7 @@ int shockidx_ctx_create(int device, shockidx_ctx **out) {
   if (e == hipSuccess) e = hipEventCreate(&c->ek0);
   if (e == hipSuccess) e = hipEventCreate(&c->ek1);
   for (int i = 0; i < NSTAGE && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&c->stage_ev[i], hipEventDisableTiming);
-  if (e == hipSuccess) e = hipMalloc((void **)&c->d_small, SMALL_BYTES);
+  if (e == hipSuccess) e = hipMalloc(&c->d_small, SMALL_BYTES);
   if (e == hipSuccess) e = hipMemsetAsync(c->d_small, 0, SMALL_BYTES, c->stream);
   if (e == hipSuccess) e = hipMemsetAsync(c->d_small + SMALL_BADKEY, 0xFF, 16, c->stream);  // both first-bad slots
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -122,9 +120,9 @@ int shockidx_ctx_create(int device, shockidx_ctx **out) {
     const int vb = sidx_cr_verify_blocks_per_cu();
     c->cr_grid = (u32)(cus * (vb < 1 ? 1 : vb));
   }
-  for (int i = 0; i < NSTAGE && e == hipSuccess; ++i) e = hipHostMalloc((void **)&c->h_stage[i], STAGE_BYTES, 0);
-  if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_res, sizeof(DevResult), 0);
-  if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_det, 64, 0);
+  for (int i = 0; i < NSTAGE && e == hipSuccess; ++i) e = hipHostMalloc(&c->h_stage[i], STAGE_BYTES, 0);
+  if (e == hipSuccess) e = hipHostMalloc(&c->h_res, sizeof(DevResult), 0);
+  if (e == hipSuccess) e = hipHostMalloc(&c->h_det, 64, 0);
   if (e == hipSuccess) {
     const unsigned hw = std::thread::hardware_concurrency();
     // 16 (a GPU's share of the host's cores on an 8-GPU MI355X node): the page-cached fd path
@@ -161,11 +159,7 @@ void shockidx_ctx_destroy(shockidx_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(c->d_in);
-  (void)hipFree(c->d_rows);
-  (void)hipFree(c->d_status);
-  (void)hipFree(c->d_detail);
-  (void)hipFree(c->d_fix);
+  c->bufs.drop_all();
   (void)hipFree(c->d_small);
   (void)hipFree(c->d_timing);
   for (int i = 0; i < NSTAGE; ++i) {
@@ -174,15 +168,6 @@ void shockidx_ctx_destroy(shockidx_ctx *c) {
   }
   if (c->h_res) (void)hipHostFree(c->h_res);
   if (c->h_det) (void)hipHostFree(c->h_det);
-  (void)hipFree(c->d_sub);
-  (void)hipFree(c->d_tile_stage);
-  (void)hipFree(c->d_tile_words);
-  (void)hipFree(c->d_fqlines);
-  (void)hipFree(c->d_cra);
-  (void)hipFree(c->d_crb);
-  (void)hipFree(c->d_cola);
-  (void)hipFree(c->d_colb);
-  for (int i = 0; i < 2; ++i) (void)hipFree(c->d_slot[i]);
   delete c->pool;
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -240,7 +225,7 @@ int shockidx_build_host(shockidx_ctx *c, const void *data, uint64_t n, int kind,
   if (int rc = build_host_pipelined(c, data, n, kind, fmt, rows, res, &piped); piped) return rc;
   if (host_pinned(data, n)) {  // registered / hipHostMalloc'ed: DMA straight from the caller's pages
     const double th = now_ms();
-    if (int rc = ensure_dev(c, (void **)&c->d_in, &c->d_in_cap, n + 64, 1, res, true)) return rc;
+    if (int rc = c->d_in.ensure(n + 64, res)) return rc;
     for (u64 off = 0; off < n; off += PIN_PIECE) {
       const u64 k = n - off < PIN_PIECE ? n - off : PIN_PIECE;
       HIPCHK(hipMemcpyAsync(c->d_in + off, (const uint8_t *)data + off, k, hipMemcpyHostToDevice, s), "H2D");
@@ -345,10 +330,7 @@ int shockidx_create(shockidx_ctx *c, int fd, uint64_t n, int kind, const char *t
     const std::string tpath = temp_idx_path(tmpdir);
     sink.fd = open(tpath.c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0666);
     if (sink.fd < 0) {
-      snprintf(res->err, sizeof res->err, "create: %s", strerror(errno));
-      res->err_len = strlen(res->err);
-      res->status = SHOCKIDX_EIO;
-      return SHOCKIDX_EIO;
+      return set_msg(res, SHOCKIDX_EIO, std::string("create: ") + strerror(errno));
     }
     bool piped = false, fell = false;
     int rc = build_fd_pipelined(c, fd, n, kind, SHOCKIDX_FMT_AUTO, sink, res, &piped, &fell);
@@ -357,10 +339,7 @@ int shockidx_create(shockidx_ctx *c, int fd, uint64_t n, int kind, const char *t
       if (ce != 0 || rename(tpath.c_str(), outpath) != 0) {  // record.go:87
         const int e = errno;
         unlink(tpath.c_str());
-        snprintf(res->err, sizeof res->err, "%s: %s", ce != 0 ? "close" : "rename", strerror(e));
-        res->err_len = strlen(res->err);
-        res->status = SHOCKIDX_EIO;
-        return SHOCKIDX_EIO;
+        return set_msg(res, SHOCKIDX_EIO, std::string(ce != 0 ? "close: " : "rename: ") + strerror(e));
       }
       res->total_ms = now_ms() - t0;
       return SHOCKIDX_OK;
@@ -373,11 +352,7 @@ int shockidx_create(shockidx_ctx *c, int fd, uint64_t n, int kind, const char *t
       if (int rc2 = fetch_rows(c, res->count, c->stream, &rows, res)) return rc2;
       int w = shockidx_write_idx(rows, res->count, tmpdir, outpath, res->err, sizeof res->err);
       free(rows);
-      if (w != SHOCKIDX_OK) {
-        res->err_len = strlen(res->err);
-        res->status = w;
-        return w;
-      }
+      if (w != SHOCKIDX_OK) return set_msg(res, w, res->err);
       res->total_ms = now_ms() - t0;
       return SHOCKIDX_OK;
     }
@@ -391,11 +366,7 @@ int shockidx_create(shockidx_ctx *c, int fd, uint64_t n, int kind, const char *t
   const double t0 = now_ms();
   int w = shockidx_write_idx(rows, res->count, tmpdir, outpath, res->err, sizeof res->err);
   free(rows);
-  if (w != SHOCKIDX_OK) {
-    res->err_len = strlen(res->err);
-    res->status = w;
-    return w;
-  }
+  if (w != SHOCKIDX_OK) return set_msg(res, w, res->err);
   res->total_ms += now_ms() - t0;
   return SHOCKIDX_OK;
 }
@@ -473,9 +444,7 @@ int shockidx_debug_inject(shockidx_ctx *c, uint32_t flags) {
 }
 
 int shockidx_slab_guess(shockidx_ctx *c, const shockidx_slab *sl, int fmt, uint64_t *guess) {
-  shockidx_result tmp;
-  shockidx_result *res = &tmp;
-  reset_result(res);
+  const Err res;  // (the text is discarded: the code is what the caller gets)
   if (!c || !sl || !guess) return SHOCKIDX_EINVAL;
   if (sl->is_first) { *guess = 0; return SHOCKIDX_OK; }
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
@@ -529,9 +498,7 @@ int shockidx_slab_index(shockidx_ctx *c, const shockidx_slab *sl, int fmt, uint6
 
 int shockidx_slab_combine(shockidx_ctx *c, const void *d_all, int world, int rank, int fmt,
                           const uint32_t *expect_seq, shockidx_slab_plan *plan) {
-  shockidx_result tmp;
-  shockidx_result *res = &tmp;
-  reset_result(res);
+  const Err res;  // (the text is discarded: the code is what the caller gets)
   if (!c || !d_all || !plan || world < 1 || world > 32 || rank < 0 || rank >= world) return SHOCKIDX_EINVAL;
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   hipStream_t s = c->stream;
@@ -598,14 +565,12 @@ int shockidx_comm_destroy(shockidx_comm *m) {
 }
 
 int shockidx_detect(shockidx_ctx *c, const void *data, uint64_t n, int *fmt, int *mask) {
-  shockidx_result tmp;
-  shockidx_result *res = &tmp;
-  reset_result(res);
+  const Err res;  // (the text is discarded: the code is what the caller gets)
   if (!c || (!data && n) || !fmt) return SHOCKIDX_EINVAL;
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   hipStream_t s = c->stream;
   const u64 m = n < 32768 ? n : 32768;
-  if (int rc = ensure_dev(c, (void **)&c->d_in, &c->d_in_cap, m + 64, 1, res, true)) return rc;
+  if (int rc = c->d_in.ensure(m + 64, res)) return rc;
   if (m) {
     memcpy(c->h_stage[0], data, m);
     HIPCHK(hipMemcpyAsync(c->d_in, c->h_stage[0], m, hipMemcpyHostToDevice, s), "H2D");

@@ -17,7 +17,7 @@ namespace {
 
 // The serial walk from (curr, cnt) for at most `steps` chunks (UINT64_MAX: to the end)
 int chunk_serial(shockidx_ctx *c, const uint8_t *dd, u64 n, int fasta, u64 chunk, u64 *rows, u64 row_cap,
-                 u64 curr, u64 cnt, u64 steps, hipStream_t s, u64 out[3], shockidx_result *res) {
+                 u64 curr, u64 cnt, u64 steps, hipStream_t s, u64 out[3], Err res) {
   u64 *d_out = (u64 *)(c->d_small + SMALL_CHUNK);
   HIPCHK(sidx_launch_chunkrecord(dd, n, fasta, (long long)chunk, rows, row_cap, d_out, (long long)curr, cnt, steps, s),
          "chunkrecord launch");
@@ -32,7 +32,7 @@ int chunk_serial(shockidx_ctx *c, const uint8_t *dd, u64 n, int fasta, u64 chunk
 // whose exact successor differs re-enters the path there (or a few serial steps first when
 // that position is not a node).  *count = rows of the serial definition.
 int chunk_spec(shockidx_ctx *c, const uint8_t *dd, u64 n, int kfmt, u64 chunk, u64 *rows, u64 row_cap,
-               hipStream_t s, u64 *count, u64 *rounds, shockidx_result *res) {
+               hipStream_t s, u64 *count, u64 *rounds, Err res) {
   const int fasta = kfmt == SHOCKIDX_FMT_FASTA;
   constexpr u64 CT = 16384;
   // rows of the path per round: about the chunk count (chunks average between chunk - 32 KiB
@@ -46,16 +46,16 @@ int chunk_spec(shockidx_ctx *c, const uint8_t *dd, u64 n, int kfmt, u64 chunk, u
   if (!fasta) {  // the FASTQ record index (valid up to its first error) gives the node positions
     u64 rcap = n / 128 + 4096;
     for (int attempt = 0; attempt < 2; ++attempt) {
-      if (int rc = ensure_dev(c, (void **)&c->d_cra, &c->cra_cap, rcap * 16, 1, res)) return rc;
+      if (int rc = c->d_cra.ensure(rcap * 16, res)) return rc;
       DevResult dr;
       shockidx_result r2;
       reset_result(&r2);
-      if (int rc = run_index(c, dd, n, F_FASTQ, (u64 *)c->d_cra, rcap, s, &dr, &r2)) return set_msg(res, rc, r2.err);
+      if (int rc = run_index(c, dd, n, F_FASTQ, c->d_cra.as<u64>(), rcap, s, &dr, &r2)) return forward_error(res, r2, rc);
       nb = dr.count;
       if (dr.flags & RF_CAPACITY) { rcap = dr.count + 1; nb = 0; continue; }
       break;
     }
-    base = (const u64 *)c->d_cra;
+    base = c->d_cra.as<u64>();
     stride = 2;
     if (nb && (3 * nb >= 0xFFFFFFF0ull)) nb = 0;
   } else {  // FASTA: every '>' preceded by '\n', plus position 0
@@ -63,7 +63,7 @@ int chunk_spec(shockidx_ctx *c, const uint8_t *dd, u64 n, int kfmt, u64 chunk, u
     size_t sb = 0;
     HIPCHK(sidx_cr_gpos_count(dd, n, nullptr, nullptr, nullptr, nullptr, &sb, s), "scan size");
     const u64 slot_bytes = 2ull * sidx_cr_gslot() * nt;
-    if (int rc = ensure_dev(c, (void **)&c->d_cra, &c->cra_cap, 16 * nt + slot_bytes + sb + 2048, 1, res)) return rc;
+    if (int rc = c->d_cra.ensure(16 * nt + slot_bytes + sb + 2048, res)) return rc;
     uint8_t *q = c->d_cra;
     u64 *tcnt = (u64 *)carve(q, 8 * nt), *toff = (u64 *)carve(q, 8 * nt);
     uint16_t *slot = (uint16_t *)carve(q, slot_bytes);
@@ -84,7 +84,7 @@ int chunk_spec(shockidx_ctx *c, const uint8_t *dd, u64 n, int kfmt, u64 chunk, u
   const u64 nn = fasta ? nb : 3 * nb;
   if (nb) {
     const u64 need = (fasta ? 8 * nb : 0) + 8 * (ntile + 2) + 12 * nn + 4 * cap + 16 * cap + 64 + 16 * 256;
-    if (int rc = ensure_dev(c, (void **)&c->d_crb, &c->crb_cap, need, 1, res)) return rc;
+    if (int rc = c->d_crb.ensure(need, res)) return rc;
     uint8_t *q = c->d_crb;
     if (fasta) {
       u64 *G = (u64 *)carve(q, 8 * nb);
@@ -205,7 +205,7 @@ int shockidx_chunkrecord_subset_device(shockidx_ctx *c, const void *d_ri, uint64
   HIPCHK(sidx_crs_scan(nullptr, R, nullptr, nullptr, nullptr, &sb, s), "scan size");
   auto r256 = [](u64 b) { return (b + 255) & ~255ull; };
   const u64 need = r256(8 * R + 8) + r256(8 * (R + 1)) + 3 * r256(4 * (R + 1)) + r256(4 * (R + 2)) + 256 + r256(sb);
-  if (int rc = ensure_dev(c, (void **)&c->d_crb, &c->crb_cap, need, 1, res)) return rc;
+  if (int rc = c->d_crb.ensure(need, res)) return rc;
   uint8_t *q = c->d_crb;
   auto carve = [&](u64 bytes) { uint8_t *r = q; q += r256(bytes); return r; };
   u64 *len = (u64 *)carve(8 * R + 8), *P = (u64 *)carve(8 * (R + 1));
@@ -254,9 +254,9 @@ int shockidx_chunkrecord_fd(shockidx_ctx *c, int fd, uint64_t n, int fmt, uint64
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   if (int rc = stage_fd(c, fd, 0, n, c->stream, res)) return rc;
   const u64 cap = n / (chunk - 32767) + 2;
-  if (int rc = ensure_dev(c, (void **)&c->d_rows, &c->d_rows_cap, cap, 16, res)) return rc;
+  if (int rc = c->d_rows.ensure(cap, res)) return rc;
   const double h2d = res->h2d_ms;
-  int rc = shockidx_chunkrecord_device(c, c->d_in, n, fmt, chunk, c->d_rows, c->d_rows_cap, res);
+  int rc = shockidx_chunkrecord_device(c, c->d_in, n, fmt, chunk, c->d_rows, c->d_rows.cap, res);
   res->h2d_ms = h2d;
   if (rc != SHOCKIDX_OK) return rc;
   if (int rc2 = fetch_rows(c, res->count, c->stream, rows, res)) return rc2;

@@ -32,11 +32,11 @@ int general_cuts(shockidx_ctx *c, const uint8_t *dd, u64 n, u32 column, hipStrea
   u64 lcap = n / 16 + 4096, L = 0;
   for (int attempt = 0;; ++attempt) {
     if (attempt == 3) return set_msg(res, SHOCKIDX_EINTERNAL, "internal error: row capacity");
-    if (int rc = ensure_dev(c, (void **)&c->d_cola, &c->cola_cap, lcap * 16, 1, res)) return rc;
+    if (int rc = c->d_cola.ensure(lcap * 16, res)) return rc;
     DevResult dr;
     shockidx_result r2;
     reset_result(&r2);
-    if (int rc = run_index(c, dd, n, F_LINE, (u64 *)c->d_cola, lcap, s, &dr, &r2)) return set_msg(res, rc, r2.err);
+    if (int rc = run_index(c, dd, n, F_LINE, c->d_cola.as<u64>(), lcap, s, &dr, &r2)) return forward_error(res, r2, rc);
     res->kernel_ms += r2.kernel_ms;
     if (dr.flags & RF_CAPACITY) {
       lcap = dr.count;
@@ -49,7 +49,7 @@ int general_cuts(shockidx_ctx *c, const uint8_t *dd, u64 n, u32 column, hipStrea
     break;
   }
   const u64 sb = sidx_col_scan_bytes(L);
-  if (int rc = ensure_dev(c, (void **)&c->d_colb, &c->colb_cap, 256 + (4 + 8 + sizeof(ColKey)) * L + sb + 4 * 256, 1, res))
+  if (int rc = c->d_colb.ensure(256 + (4 + 8 + sizeof(ColKey)) * L + sb + 4 * 256, res))
     return rc;
   Carver cv{c->d_colb};
   u64 *ctl = cv.take<u64>(COL_CTL_WORDS);
@@ -59,7 +59,7 @@ int general_cuts(shockidx_ctx *c, const uint8_t *dd, u64 n, u32 column, hipStrea
   void *scan_tmp = cv.take<uint8_t>(sb);
   *ctl_out = ctl;
   HIPCHK(hipEventRecord(c->ev0, s), "event");
-  HIPCHK(sidx_col_cuts(dd, n, (u64 *)c->d_cola, L, column, flag, rank, ck, ctl, scan_tmp, sb, s), "column launch");
+  HIPCHK(sidx_col_cuts(dd, n, c->d_cola.as<u64>(), L, column, flag, rank, ck, ctl, scan_tmp, sb, s), "column launch");
   return 0;
 }
 
@@ -73,7 +73,7 @@ int column_build(shockidx_ctx *c, const uint8_t *dd, u64 n, u32 column, bool own
   const u64 *ctl = nullptr;
   if (tiles) {
     const u64 nt = (n + TILE - 1) / TILE;
-    if (int rc = ensure_dev(c, (void **)&c->d_colb, &c->colb_cap, sidx_col_tile_bytes(nt), 1, res)) return rc;
+    if (int rc = c->d_colb.ensure(sidx_col_tile_bytes(nt), res)) return rc;
     HIPCHK(hipEventRecord(c->ev0, s), "event");
     HIPCHK(sidx_col_tile_cuts(dd, n, column, c->tiles_grid, c->d_colb, &ctl, s), "column tile pass launch");
   } else if (int rc = general_cuts(c, dd, n, column, s, &ctl, res)) {
@@ -86,15 +86,15 @@ int column_build(shockidx_ctx *c, const uint8_t *dd, u64 n, u32 column, bool own
   if (h[COL_BAD] != ~0ull) return set_msg(res, SHOCKIDX_EFORMAT, COLUMN_MISSING);
   const u64 B = h[COL_B], count = B ? B + 1 : 0;
   if (own) {
-    if (int rc = ensure_dev(c, (void **)&c->d_rows, &c->d_rows_cap, count ? count : 1, 16, res)) return rc;
+    if (int rc = c->d_rows.ensure(count ? count : 1, res)) return rc;
     d_rows = c->d_rows;
-    row_cap = c->d_rows_cap;
+    row_cap = c->d_rows.cap;
   }
   res->count = count;
   if (count > row_cap) return set_msg(res, SHOCKIDX_ESPACE, "row capacity too small");
   if (count) {
     if (tiles) HIPCHK(sidx_col_tile_rows(n, c->d_colb, count, d_rows, row_cap, s), "column rows launch");
-    else HIPCHK(sidx_col_rows((const u64 *)c->d_cola, ctl, B, n, d_rows, row_cap, s), "column rows launch");
+    else HIPCHK(sidx_col_rows(c->d_cola.as<u64>(), ctl, B, n, d_rows, row_cap, s), "column rows launch");
     HIPCHK(hipEventRecord(c->ev1, s), "event");
     if (verify_rows()) {  // SHOCKIDX_VERIFY: contiguous rows from 0 to n
       DevResult *d_res = (DevResult *)(c->d_small + SMALL_RESULT);

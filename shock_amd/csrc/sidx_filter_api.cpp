@@ -17,6 +17,15 @@ using namespace sidx_host;
 
 namespace {
 
+// The output offsets of K delivered items (the exclusive scan of their lengths) and the bytes
+// they take together, waited for; K = 0: nothing is launched.
+int scan_lengths(shockidx_ctx *c, const u64 *len, u64 *off, u64 K, void *tmp, size_t *tmp_bytes, u64 *total, Err res) {
+  *total = 0;
+  if (!K) return 0;
+  HIPCHK(sidx_scan_u64(len, off, K, tmp, tmp_bytes, c->stream), "scan");
+  return scan_total(c, off, len, K, total, res);
+}
+
 // anonymize over a FASTA or SAM section (anonymize.go:28-56 through multi.Reader): the stream
 // Read + Format deliver (sidx_filter.hip), count / size delivered, Read's error text.
 int anonymize_other(shockidx_ctx *c, const uint8_t *dd, u64 n, int kfmt, uint8_t *d_out, u64 out_cap,
@@ -36,68 +45,49 @@ int anonymize_other(shockidx_ctx *c, const uint8_t *dd, u64 n, int kfmt, uint8_t
     // found by the FASTA tile pass in one read.  Otherwise (the index validates pieces Read does
     // not) they come from the unvalidated scan below.
     const int brc = build_resident(c, dd, n, SHOCKIDX_RECORD, SHOCKIDX_FMT_FASTA, s, &br);
-    if (brc < 0) return sub_msg(res, brc, std::string(br.err, br.err_len));
+    if (brc < 0) return forward_error(res, br, brc);
     if (brc == SHOCKIDX_OK) {
       indexed = true;
       res->kernel_ms += br.kernel_ms;
       K = br.count ? br.count - 1 : 0;
       B = c->d_rows + 2;
       bstride = 2;
-      SUBCHK(sidx_scan_u64(nullptr, nullptr, K ? K : 1, nullptr, &tb, s), "scan size");
-      shockidx_result wr;
-      memset(&wr, 0, sizeof wr);
-      if (int rc = ensure_dev(c, (void **)&c->d_sub, &c->d_sub_cap, 8 * (K + 1) + 48 * (K + 1) + tb + 4096, 1, &wr))
-        return sub_msg(res, rc, wr.err);
-      SUBCHK(hipEventRecord(c->ek0, s), "event");
+      HIPCHK(sidx_scan_u64(nullptr, nullptr, K ? K : 1, nullptr, &tb, s), "scan size");
+      if (int rc = c->d_sub.ensure(8 * (K + 1) + 48 * (K + 1) + tb + 4096, res)) return rc;
+      HIPCHK(hipEventRecord(c->ek0, s), "event");
     }
   }
   if (fasta && !indexed) {
     const u64 nt = (n + TILE - 1) / TILE;
     size_t fb = 0;
-    SUBCHK(sidx_fa_bnd_count(dd, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &fb, s),
+    HIPCHK(sidx_fa_bnd_count(dd, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &fb, s),
            "scan size");
     const u64 slot_bytes = 2ull * sidx_fa_slot() * (nt + 1);
     const u64 need = 6 * 8 * (nt + 1) + slot_bytes + fb + 8 * 256;
-    {
-      shockidx_result wr;
-      memset(&wr, 0, sizeof wr);
-      if (int rc = ensure_dev(c, (void **)&c->d_cra, &c->cra_cap, need, 1, &wr)) return sub_msg(res, rc, wr.err);
-    }
+    if (int rc = c->d_cra.ensure(need, res)) return rc;
     Carver cv{c->d_cra};
     u64 *lnl = cv.take<u64>(nt + 1), *lgt = cv.take<u64>(nt + 1), *cnl = cv.take<u64>(nt + 1);
     u64 *cgt = cv.take<u64>(nt + 1), *tcnt = cv.take<u64>(nt + 1), *toff = cv.take<u64>(nt + 1);
     uint16_t *slot = cv.take<uint16_t>(sidx_fa_slot() * (nt + 1));
     void *tmp = cv.take<uint8_t>(fb);
-    SUBCHK(hipEventRecord(c->ek0, s), "event");
-    SUBCHK(sidx_fa_bnd_count(dd, n, lnl, lgt, cnl, cgt, tcnt, toff, slot, tmp, &fb, s), "boundaries");
-    if (nt) {
-      u64 a = 0, b = 0;
-      if (int rc = d2h(c, &a, toff + nt - 1, res)) return rc;
-      if (int rc = d2h(c, &b, tcnt + nt - 1, res)) return rc;
-      K = a + b;
-    }
-    SUBCHK(sidx_scan_u64(nullptr, nullptr, K ? K : 1, nullptr, &tb, s), "scan size");
-    {
-      shockidx_result wr;
-      memset(&wr, 0, sizeof wr);
-      const u64 need2 = 8 * (K + 1) + 48 * (K + 1) + tb + 4096;
-      if (int rc = ensure_dev(c, (void **)&c->d_sub, &c->d_sub_cap, need2, 1, &wr)) return sub_msg(res, rc, wr.err);
-    }
-    u64 *Bw = (u64 *)c->d_sub;
-    SUBCHK(sidx_fa_bnd_write(dd, n, cnl, cgt, tcnt, toff, slot, Bw, s), "boundary positions");
+    HIPCHK(hipEventRecord(c->ek0, s), "event");
+    HIPCHK(sidx_fa_bnd_count(dd, n, lnl, lgt, cnl, cgt, tcnt, toff, slot, tmp, &fb, s), "boundaries");
+    if (nt)
+      if (int rc = scan_total(c, toff, tcnt, nt, &K, res)) return rc;
+    HIPCHK(sidx_scan_u64(nullptr, nullptr, K ? K : 1, nullptr, &tb, s), "scan size");
+    if (int rc = c->d_sub.ensure(8 * (K + 1) + 48 * (K + 1) + tb + 4096, res)) return rc;
+    u64 *Bw = c->d_sub.as<u64>();
+    HIPCHK(sidx_fa_bnd_write(dd, n, cnl, cgt, tcnt, toff, slot, Bw, s), "boundary positions");
     B = Bw;
   } else if (!fasta) {
     const int brc = build_resident(c, dd, n, SHOCKIDX_LINE, SHOCKIDX_FMT_AUTO, s, &br);  // ReadBytes('\n')
-    if (brc != SHOCKIDX_OK) return sub_msg(res, brc < 0 ? brc : SHOCKIDX_EINTERNAL, std::string(br.err, br.err_len));
+    if (brc != SHOCKIDX_OK) return forward_error(res, br, brc < 0 ? brc : SHOCKIDX_EINTERNAL);
     res->kernel_ms += br.kernel_ms;
     K = br.count;
     B = c->d_rows;
-    SUBCHK(sidx_scan_u64(nullptr, nullptr, K ? K : 1, nullptr, &tb, s), "scan size");
-    shockidx_result wr;
-    memset(&wr, 0, sizeof wr);
-    if (int rc = ensure_dev(c, (void **)&c->d_sub, &c->d_sub_cap, 48 * (K + 1) + tb + 4096, 1, &wr))
-      return sub_msg(res, rc, wr.err);
-    SUBCHK(hipEventRecord(c->ek0, s), "event");
+    HIPCHK(sidx_scan_u64(nullptr, nullptr, K ? K : 1, nullptr, &tb, s), "scan size");
+    if (int rc = c->d_sub.ensure(48 * (K + 1) + tb + 4096, res)) return rc;
+    HIPCHK(hipEventRecord(c->ek0, s), "event");
   }
   Carver cv{c->d_sub};
   if (fasta) (void)cv.take<u64>(K + 1);  // the boundary positions
@@ -106,42 +96,36 @@ int anonymize_other(shockidx_ctx *c, const uint8_t *dd, u64 n, int kfmt, uint8_t
   u64 *outlen = cv.take<u64>(K + 1);
   u64 *outoff = cv.take<u64>(K + 1);
   void *scan_tmp = cv.take<uint8_t>(tb);
-  SUBCHK(hipMemsetAsync(small, 0xFF, 16, s), "memset");
-  SUBCHK(hipMemsetAsync(small + 2, 0, 8, s), "memset");
-  if (fasta) SUBCHK(sidx_fa_anon_spans(dd, n, B, bstride, K, span, outlen, small, s), "anonymize spans");
-  else SUBCHK(sidx_sam_anon_spans(dd, n, B, K, span, outlen, small, small + 1, s), "anonymize spans");
+  HIPCHK(hipMemsetAsync(small, 0xFF, 16, s), "memset");
+  HIPCHK(hipMemsetAsync(small + 2, 0, 8, s), "memset");
+  if (fasta) HIPCHK(sidx_fa_anon_spans(dd, n, B, bstride, K, span, outlen, small, s), "anonymize spans");
+  else HIPCHK(sidx_sam_anon_spans(dd, n, B, K, span, outlen, small, small + 1, s), "anonymize spans");
   u64 st[2] = {~0ull, ~0ull};
-  SUBCHK(hipMemcpyAsync(st, small, 16, hipMemcpyDeviceToHost, s), "status copy");
-  SUBCHK(hipStreamSynchronize(s), "status sync");
+  HIPCHK(hipMemcpyAsync(st, small, 16, hipMemcpyDeviceToHost, s), "status copy");
+  HIPCHK(hipStreamSynchronize(s), "status sync");
   const u64 bad = st[0], eof = fasta ? ~0ull : st[1];
   const u64 Ke = bad < K && bad < eof ? bad : (eof < K ? eof : K);  // the items Read delivers
   const bool err = bad < K && bad < eof;
   u64 total = 0;
-  if (Ke) {
-    SUBCHK(sidx_scan_u64(outlen, outoff, Ke, scan_tmp, &tb, s), "scan");
-    u64 lo = 0, ll = 0;
-    if (int rc = d2h(c, &lo, outoff + Ke - 1, res)) return rc;
-    if (int rc = d2h(c, &ll, outlen + Ke - 1, res)) return rc;
-    total = lo + ll;
-  }
+  if (int rc = scan_lengths(c, outlen, outoff, Ke, scan_tmp, &tb, &total, res)) return rc;
   res->size = total;
   res->count = fasta ? Ke : 0;
-  if (total > out_cap) return sub_msg(res, SHOCKIDX_ESPACE, "output capacity too small");
-  if (fasta) SUBCHK(sidx_fa_anon_write(dd, n, span, outoff, Ke, d_out, s), "anonymize write");
-  else SUBCHK(sidx_sam_anon_write(dd, span, outlen, outoff, Ke, d_out, small + 2, s), "anonymize write");
-  SUBCHK(hipEventRecord(c->ek1, s), "event");
+  if (total > out_cap) return set_msg(res, SHOCKIDX_ESPACE, "output capacity too small");
+  if (fasta) HIPCHK(sidx_fa_anon_write(dd, n, span, outoff, Ke, d_out, s), "anonymize write");
+  else HIPCHK(sidx_sam_anon_write(dd, span, outlen, outoff, Ke, d_out, small + 2, s), "anonymize write");
+  HIPCHK(hipEventRecord(c->ek1, s), "event");
   if (!fasta) {
     u64 cnt = 0;
     if (int rc = d2h(c, &cnt, small + 2, res)) return rc;
     res->count = cnt;
   }
-  SUBCHK(hipStreamSynchronize(s), "anonymize sync");
+  HIPCHK(hipStreamSynchronize(s), "anonymize sync");
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, c->ek0, c->ek1);
   res->kernel_ms += ms;
   res->total_ms = now_ms() - t0;
   if (!err) return SHOCKIDX_OK;
-  return sub_msg(res, SHOCKIDX_EFORMAT, fasta ? "Invalid fasta entry" : "sam alignment fields less than 11");
+  return set_msg(res, SHOCKIDX_EFORMAT, fasta ? "Invalid fasta entry" : "sam alignment fields less than 11");
 }
 
 }  // namespace
@@ -153,43 +137,38 @@ int shockidx_filter_device(shockidx_ctx *c, const char *filter, const void *d_da
                            uint64_t out_cap, shockidx_subset_result *res) {
   shockidx_subset_result tmp;
   if (!res) res = &tmp;
-  sub_reset(res);
+  reset_result(res);
   if (!c || !filter || (!d_data && n) || ((uintptr_t)d_data & 15) || (!d_out && out_cap))
-    return sub_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+    return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
   int kind = 0;  // filter.go:13-16
   if (!strcmp(filter, "fq2fa")) kind = 1;
   else if (!strcmp(filter, "anonymize")) kind = 2;
-  else return sub_msg(res, SHOCKIDX_EINVAL, "unknown filter");
+  else return set_msg(res, SHOCKIDX_EINVAL, "unknown filter");
   const double t0 = now_ms();
-  SUBCHK(hipSetDevice(c->device), "hipSetDevice");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   hipStream_t s = c->stream;
   const uint8_t *dd = (const uint8_t *)d_data;
-  shockidx_result br;
-  reset_result(&br);
   if (kind == 2) {  // anonymize reads through multi.Reader: DetermineFormat first (multi.go:43-62)
     int kfmt = 0;
-    if (int rc = resolve_format(c, dd, n, SHOCKIDX_RECORD, SHOCKIDX_FMT_AUTO, s, &kfmt, &br))
-      return sub_msg(res, rc, std::string(br.err, br.err_len));
+    if (int rc = resolve_format(c, dd, n, SHOCKIDX_RECORD, SHOCKIDX_FMT_AUTO, s, &kfmt, res)) return rc;
     if (kfmt != SHOCKIDX_FMT_FASTQ) return anonymize_other(c, dd, n, kfmt, (uint8_t *)d_out, out_cap, res, t0);
   }
   // the record index (GetReadOffset) gives the record boundaries up to its first error; its tile
   // pass keeps every record's line ends for the spans
+  shockidx_result br;
+  reset_result(&br);
   c->want_spans = !getenv("SHOCKIDX_FILTER_RESCAN");
   const int brc = build_resident(c, dd, n, SHOCKIDX_RECORD, SHOCKIDX_FMT_FASTQ, s, &br);
   c->want_spans = false;
-  if (brc < 0) return sub_msg(res, brc, std::string(br.err, br.err_len));
+  if (brc < 0) return forward_error(res, br, brc);
   const u64 K = br.count;
   res->kernel_ms += br.kernel_ms;
   size_t scan_bytes = 0;
-  SUBCHK(sidx_scan_u64(nullptr, nullptr, K ? K : 1, nullptr, &scan_bytes, s), "scan size");
+  HIPCHK(sidx_scan_u64(nullptr, nullptr, K ? K : 1, nullptr, &scan_bytes, s), "scan size");
   // the output blocks' first records: the output is at most the section + 11 bytes per record
   const u64 nwf = (n + 11 * K) / sidx_filter_block() + 4;
   const u64 need = 48 * (K + 8) + scan_bytes + 8 * nwf + 4096;
-  {
-    shockidx_result wr;
-    memset(&wr, 0, sizeof wr);
-    if (int rc = ensure_dev(c, (void **)&c->d_sub, &c->d_sub_cap, need, 1, &wr)) return sub_msg(res, rc, wr.err);
-  }
+  if (int rc = c->d_sub.ensure(need, res)) return rc;
   Carver cv{c->d_sub};
   u64 *small = cv.take<u64>(8);
   u32 *spans = cv.take<u32>(6 * (K + 1));
@@ -197,13 +176,13 @@ int shockidx_filter_device(shockidx_ctx *c, const char *filter, const void *d_da
   u64 *outoff = cv.take<u64>(K + 1);
   void *scan_tmp = cv.take<uint8_t>(scan_bytes);
   u64 *wfirst = cv.take<u64>(nwf);
-  SUBCHK(hipEventRecord(c->ek0, s), "event");
-  SUBCHK(hipMemsetAsync(small, 0xFF, 8, s), "memset");
+  HIPCHK(hipEventRecord(c->ek0, s), "event");
+  HIPCHK(hipMemsetAsync(small, 0xFF, 8, s), "memset");
   if (c->last_spans && K) {  // the certified records' spans from the tile pass; k_fq_spans does the rest
-    SUBCHK(hipMemsetAsync(outlen, 0, 8 * K, s), "memset");
-    SUBCHK(sidx_launch_fq_spans_place(&c->last_p, spans, outlen, K, kind, s), "spans place");
+    HIPCHK(hipMemsetAsync(outlen, 0, 8 * K, s), "memset");
+    HIPCHK(sidx_launch_fq_spans_place(&c->last_p, spans, outlen, K, kind, s), "spans place");
   }
-  SUBCHK(sidx_filter_spans(dd, n, c->d_rows, K, kind, spans, outlen, small, s), "filter spans");
+  HIPCHK(sidx_filter_spans(dd, n, c->d_rows, K, kind, spans, outlen, small, s), "filter spans");
   u64 firstbad = ~0ull;
   if (int rc = d2h(c, &firstbad, small, res)) return rc;
   // Read()'s first failing record: one the index accepted but Read rejects (a blank-looking ID
@@ -215,43 +194,37 @@ int shockidx_filter_device(shockidx_ctx *c, const char *filter, const void *d_da
     code = (u32)(firstbad & 15);
   } else if (brc == SHOCKIDX_EFORMAT) {
     u64 last[2] = {0, 0};
-    if (K) SUBCHK(hipMemcpyAsync(last, c->d_rows + 2 * (K - 1), 16, hipMemcpyDeviceToHost, s), "row copy");
-    SUBCHK(sidx_filter_read_status(dd, n, K ? last[0] + last[1] : 0, (u32 *)(small + 1), s), "read status");
+    if (K) HIPCHK(hipMemcpyAsync(last, c->d_rows + 2 * (K - 1), 16, hipMemcpyDeviceToHost, s), "row copy");
+    HIPCHK(sidx_filter_read_status(dd, n, K ? last[0] + last[1] : 0, (u32 *)(small + 1), s), "read status");
     u32 st = 0;
     if (int rc = d2h(c, &st, small + 1, res)) return rc;
-    if (st == ST_OK || st == ST_END) return sub_msg(res, SHOCKIDX_EINTERNAL, "internal error: filter terminal record");
+    if (st == ST_OK || st == ST_END) return set_msg(res, SHOCKIDX_EINTERNAL, "internal error: filter terminal record");
     code = st;
   } else if (K) {  // the last record's quality line ends at EOF: Read returns it with io.EOF, dropped
     u64 last[2] = {0, 0};
     uint8_t lastb = '\n';
-    SUBCHK(hipMemcpyAsync(last, c->d_rows + 2 * (K - 1), 16, hipMemcpyDeviceToHost, s), "row copy");
-    if (n) SUBCHK(hipMemcpyAsync(&lastb, dd + n - 1, 1, hipMemcpyDeviceToHost, s), "byte copy");
-    SUBCHK(hipStreamSynchronize(s), "sync");
+    HIPCHK(hipMemcpyAsync(last, c->d_rows + 2 * (K - 1), 16, hipMemcpyDeviceToHost, s), "row copy");
+    if (n) HIPCHK(hipMemcpyAsync(&lastb, dd + n - 1, 1, hipMemcpyDeviceToHost, s), "byte copy");
+    HIPCHK(hipStreamSynchronize(s), "sync");
     if (last[0] + last[1] == n && lastb != '\n') Ke = K - 1;
   }
   u64 total = 0;
-  if (Ke) {
-    SUBCHK(sidx_scan_u64(outlen, outoff, Ke, scan_tmp, &scan_bytes, s), "scan");
-    u64 lo = 0, ll = 0;
-    if (int rc = d2h(c, &lo, outoff + Ke - 1, res)) return rc;
-    if (int rc = d2h(c, &ll, outlen + Ke - 1, res)) return rc;
-    total = lo + ll;
-  }
+  if (int rc = scan_lengths(c, outlen, outoff, Ke, scan_tmp, &scan_bytes, &total, res)) return rc;
   res->count = Ke;
   res->size = total;
-  if (total > out_cap) return sub_msg(res, SHOCKIDX_ESPACE, "output capacity too small");
-  if (total / sidx_filter_block() + 1 > nwf) return sub_msg(res, SHOCKIDX_EINTERNAL, "internal error: filter plan size");
-  SUBCHK(sidx_filter_write(dd, n, c->d_rows, spans, outlen, outoff, Ke, total, kind, wfirst, (uint8_t *)d_out, s),
+  if (total > out_cap) return set_msg(res, SHOCKIDX_ESPACE, "output capacity too small");
+  if (total / sidx_filter_block() + 1 > nwf) return set_msg(res, SHOCKIDX_EINTERNAL, "internal error: filter plan size");
+  HIPCHK(sidx_filter_write(dd, n, c->d_rows, spans, outlen, outoff, Ke, total, kind, wfirst, (uint8_t *)d_out, s),
          "filter write");
-  SUBCHK(hipEventRecord(c->ek1, s), "event");
-  SUBCHK(hipStreamSynchronize(s), "filter sync");
+  HIPCHK(hipEventRecord(c->ek1, s), "event");
+  HIPCHK(hipStreamSynchronize(s), "filter sync");
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, c->ek0, c->ek1);
   res->kernel_ms += ms;
   res->total_ms = now_ms() - t0;
   if (code == ST_END) return SHOCKIDX_OK;
   const char *m = status_message(code);
-  return sub_msg(res, SHOCKIDX_EFORMAT, m ? m : "internal error: filter status");
+  return set_msg(res, SHOCKIDX_EFORMAT, m ? m : "internal error: filter status");
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // sidx_host.hpp -- the host side of libshockidx as its translation units see each other: the
-// context, the error helpers, and the functions of sidx_build.cpp (workspaces, one index pass,
-// staging, copy-out) and sidx_pipeline.cpp (the slab pipelines) that the entry points call.
+// context and its device caches (sidx_devbuf.hpp), the error helpers, and the functions of
+// sidx_build.cpp (workspaces, one index pass, staging, copy-out) and sidx_pipeline.cpp (the slab
+// pipelines) that the entry points call.
 // Internal: not part of the C ABI (include/shockidx.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@
 
 #include "../../include/shockidx.h"
 #include "sidx_common.hpp"
+#include "sidx_devbuf.hpp"
 
 namespace sidx_host {
 
@@ -59,21 +61,42 @@ class CopyPool {
 
 }  // namespace sidx_host
 
+// Device memory; node = a node body the tile passes stream (the context's input staging,
+// shockidx_dev_alloc_node): physically contiguous when the driver can (hipDeviceMallocContiguous),
+// else plain hipMalloc.  10 GiB FASTQ, interleaved allocations in one process on MI355X:
+// k_fq_tiles 1.93-1.95 ms (median) from contiguous memory in 5 of 5 allocations, 1.92-2.15 ms from
+// hipMalloc'd memory depending on where it landed (tools/placement_probe2.py,
+// profiles/r04/placement2b.txt).  Written buffers (row tables, tile words) stay plain: the row
+// placement ran 0.13 -> 0.18 ms into contiguous memory.  Freed with hipFree.
+namespace sidx_host {
+hipError_t dev_malloc(void **p, size_t bytes, bool node);
+const DevAlloc *hip_allocator();  // dev_malloc / hipFree / hipGetErrorString
+}  // namespace sidx_host
+
+// The context.  Its device caches are the DevBuf members: each registers with `bufs`, which is
+// what shockidx_ctx_workspace_bytes counts, what a trim drops (large buffers first, the tile block
+// last) and what shockidx_ctx_destroy frees -- a new cache is one declaration here.  They grow on
+// demand (DevBuf::ensure) and stay until a trim; the two slab slots are exact-size.  d_small,
+// d_timing and the pinned host buffers are fixed-size, outside the count and the trims.
 struct shockidx_ctx {
   typedef sidx::u64 u64;
   typedef sidx::u32 u32;
+  template <class T, size_t PER = 1> using Buf = sidx_host::DevBuf<T, PER>;
+  typedef sidx_host::BufClass BufClass;
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ek0 = nullptr, ek1 = nullptr;
   hipEvent_t stage_ev[sidx_host::NSTAGE] = {nullptr, nullptr};
-  uint8_t *d_in = nullptr;
-  u64 d_in_cap = 0;
-  u64 *d_rows = nullptr;
-  u64 d_rows_cap = 0;  // rows
-  u64 *d_status = nullptr;  // STATUS_ARRAYS sub-arrays of tiles_cap words each (StatusArray)
-  u64 *d_detail = nullptr;
-  u64 *d_fix = nullptr;  // k_fixup queue (FixRec, 24 bytes each), tiles_cap items
-  u64 tiles_cap = 0;
+  sidx_host::BufSet bufs{sidx_host::hip_allocator()};
+  Buf<uint8_t> d_in{bufs, BufClass::Large, true};  // input staging (node memory)
+  Buf<u64, 2> d_rows{bufs};                        // the row table (capacity in rows)
+  // the tile block: grown together by ensure_tiles for tiles_cap() tiles
+  // (d_status: STATUS_ARRAYS sub-arrays of tiles_cap() words, StatusArray; d_detail: 4 words per
+  // tile; d_fix: the k_fixup queue, FixRec of 24 bytes each, tiles_cap() items)
+  Buf<u64> d_status{bufs, BufClass::Tile, false, "hipMalloc(status)"};
+  Buf<u64> d_detail{bufs, BufClass::Tile, false, "hipMalloc(detail)"};
+  Buf<u64> d_fix{bufs, BufClass::Tile, false, "hipMalloc(fix)"};
+  u64 tiles_cap() const { return d_fix.cap / 4; }
   uint8_t *d_small = nullptr;  // badkey[2] | counters[2][NCOUNTERS] | result | detect
   u32 epoch = 0;               // build epoch for the look-back words (1..EPOCH_MASK)
   bool slots_dirty = false;    // a build took an epoch and did not reach its finalize
@@ -83,33 +106,26 @@ struct shockidx_ctx {
   uint8_t *h_stage[sidx_host::NSTAGE] = {nullptr, nullptr};
   sidx::DevResult *h_res = nullptr;
   sidx_host::CopyPool *pool = nullptr;  // host memcpy threads for the host-memory entry points
-  uint8_t *d_sub = nullptr;        // subset / gather workspace
-  u64 d_sub_cap = 0;
+  Buf<uint8_t> d_sub{bufs};        // subset / gather workspace (bytes)
   int *h_det = nullptr;
   u64 ws_cap = 0;                  // SHOCKIDX_WORKSPACE_CAP: trim the caches above this after a call
   u64 dev_cap = 0;                 // device bytes a build may hold (0: what the device has free;
                                    //   shockidx_ctx_set_dev_cap / SHOCKIDX_DEV_CAP)
-  u32 *d_tile_stage = nullptr;     // tile passes: staged positions (tile_stage_words() u32 entries)
-  u64 tile_stage_cap = 0;
-  u32 *d_tile_words = nullptr;     //   per-tile results (FQ_TILE_WORDS per tile)
-  u64 tile_words_cap = 0;
-  uint8_t *d_cra = nullptr;        // speculative chunkrecord: FASTQ record table / FASTA tile counts
-  u64 cra_cap = 0;                 //   (bytes)
-  uint8_t *d_crb = nullptr;        //   node positions, jump tables, path, results (bytes)
-  uint8_t *d_slot[2] = {nullptr, nullptr};  // fd builds within the device cap: the two slab slots
-  u64 slot_cap = 0;                //   (bytes each)
-  u64 crb_cap = 0;
+  Buf<u32> d_tile_stage{bufs};     // tile passes: staged positions (tile_stage_words() u32 entries)
+  Buf<u32> d_tile_words{bufs};     //   per-tile results (FQ_TILE_WORDS per tile)
+  Buf<uint8_t> d_cra{bufs};        // speculative chunkrecord: FASTQ record table / FASTA tile counts (bytes)
+  Buf<uint8_t> d_crb{bufs};        //   node positions, jump tables, path, results (bytes)
+  // fd builds within the device cap: the two slab slots (exact-size, bytes each)
+  Buf<uint8_t> d_slot[2] = {Buf<uint8_t>{bufs, BufClass::Large, true, "hipMalloc(slab slot)"},
+                            Buf<uint8_t>{bufs, BufClass::Large, true, "hipMalloc(slab slot)"}};
   u32 cr_grid = 0;                 //   k_cr_verify persistent grid
-  uint8_t *d_cola = nullptr;       // column index: the line table, then the cut offsets (bytes)
-  u64 cola_cap = 0;
-  uint8_t *d_colb = nullptr;       //   flags, ranks, key spans, scan workspace (bytes)
-  u64 colb_cap = 0;
+  Buf<uint8_t> d_cola{bufs};       // column index: the line table, then the cut offsets (bytes)
+  Buf<uint8_t> d_colb{bufs};       //   flags, ranks, key spans, scan workspace (bytes)
   hipStream_t s_copy = nullptr;    // slab-pipelined host builds: the H2D stream
   uint8_t *h_rows[2] = {nullptr, nullptr};  // slab-pipelined fd builds: pinned row staging (D2H)
   // download filters over FASTQ: the tile pass keeps each record's line ends (k_fq_tiles<true>)
   bool want_spans = false;
-  uint16_t *d_fqlines = nullptr;
-  u64 fqlines_cap = 0;             //   (u16 entries)
+  Buf<uint16_t> d_fqlines{bufs};   //   (u16 entries)
   sidx::SlabParams last_p;         // the last FASTQ tile pass's parameters (k_fq_spans_place)
   bool last_spans = false;         //   its line ends are in d_fqlines
   // test hooks (shockidx_debug_inject, not in the public header): bit0 a freshly grown status
@@ -121,15 +137,15 @@ struct shockidx_ctx {
 
 namespace sidx_host {
 
-// ---- results and errors ----------------------------------------------------------------------
-int set_msg(shockidx_result *r, int code, const char *msg);
-int set_hip(shockidx_result *r, hipError_t e, const char *what);
-inline void reset_result(shockidx_result *r) {
+// ---- results and errors (the sink and set_msg: sidx_devbuf.hpp) ------------------------------
+int set_hip(Err r, hipError_t e, const char *what);
+template <class R> void reset_result(R *r) {
   if (r) memset(r, 0, sizeof *r);
 }
 // Go's text for a FASTQ status code (ST_*), nullptr for codes without one
 const char *status_message(uint32_t code);
 
+// (expects an error sink or a result pointer named res in scope)
 #define HIPCHK(expr, what)                      \
   do {                                          \
     hipError_t _e = (expr);                     \
@@ -139,27 +155,15 @@ const char *status_message(uint32_t code);
 // fasta.go:115-121: fmt.Errorf("Invalid fasta entry: %s", read[0:min(50, len(read))]) into res;
 // read_piece(dst, k) fetches the piece's first k bytes (0, or its error code with res set).
 template <class Read>
-int fasta_error_text(shockidx_result *res, uint64_t err_len, Read read_piece) {
+int fasta_error_text(Err res, uint64_t err_len, Read read_piece) {
   static const char pre[] = "Invalid fasta entry: ";
+  char text[sizeof pre - 1 + 50];
   const uint64_t show = err_len < 50 ? err_len : 50;
-  memcpy(res->err, pre, sizeof pre - 1);
+  memcpy(text, pre, sizeof pre - 1);
   if (show)
-    if (int rc = read_piece(res->err + sizeof pre - 1, show)) return rc;
-  res->err_len = sizeof pre - 1 + show;
-  res->err[res->err_len] = 0;
-  res->status = SHOCKIDX_EFORMAT;
-  return SHOCKIDX_EFORMAT;
+    if (int rc = read_piece(text + sizeof pre - 1, show)) return rc;
+  return set_msg(res, SHOCKIDX_EFORMAT, text, sizeof pre - 1 + show);
 }
-
-// the subset / filter entry points' result (shockidx_subset_result)
-inline void sub_reset(shockidx_subset_result *r) { memset(r, 0, sizeof *r); }
-int sub_msg(shockidx_subset_result *r, int code, const std::string &m);
-int sub_hip(shockidx_subset_result *r, hipError_t e, const char *what);
-#define SUBCHK(expr, what)                                 \
-  do {                                                     \
-    hipError_t _e = (expr);                                \
-    if (_e != hipSuccess) return sidx_host::sub_hip(res, _e, what);   \
-  } while (0)
 
 // carve 256-byte-aligned pieces out of a device workspace
 struct Carver {
@@ -174,27 +178,27 @@ struct Carver {
 
 // one T from device memory, waited for
 template <class T>
-int d2h(shockidx_ctx *c, T *dst, const void *src, shockidx_subset_result *res) {
-  SUBCHK(hipMemcpyAsync(dst, src, sizeof(T), hipMemcpyDeviceToHost, c->stream), "subset copy");
-  SUBCHK(hipStreamSynchronize(c->stream), "subset sync");
+int d2h(shockidx_ctx *c, T *dst, const void *src, Err res) {
+  HIPCHK(hipMemcpyAsync(dst, src, sizeof(T), hipMemcpyDeviceToHost, c->stream), "subset copy");
+  HIPCHK(hipStreamSynchronize(c->stream), "subset sync");
+  return 0;
+}
+// the total of an exclusive scan of K > 0 lengths: off[K - 1] + len[K - 1], waited for
+template <class L>
+int scan_total(shockidx_ctx *c, const sidx::u64 *off, const L *len, sidx::u64 K, sidx::u64 *total, Err res) {
+  sidx::u64 lo = 0;
+  L ll = 0;
+  if (int rc = d2h(c, &lo, off + K - 1, res)) return rc;
+  if (int rc = d2h(c, &ll, len + K - 1, res)) return rc;
+  *total = lo + ll;
   return 0;
 }
 
-// ---- device memory and the context's caches (sidx_build.cpp) ---------------------------------
-// Device memory; node = a node body the tile passes stream (the context's input staging,
-// shockidx_dev_alloc_node): physically contiguous when the driver can (hipDeviceMallocContiguous),
-// else plain hipMalloc.  10 GiB FASTQ, interleaved allocations in one process on MI355X:
-// k_fq_tiles 1.93-1.95 ms (median) from contiguous memory in 5 of 5 allocations, 1.92-2.15 ms from
-// hipMalloc'd memory depending on where it landed (tools/placement_probe2.py,
-// profiles/r04/placement2b.txt).  Written buffers (row tables, tile words) stay plain: the row
-// placement ran 0.13 -> 0.18 ms into contiguous memory.  Freed with hipFree.
-hipError_t dev_malloc(void **p, size_t bytes, bool node);
-// grow-only: *p holds at least `need` elements of `elem` bytes afterwards
-int ensure_dev(shockidx_ctx *c, void **p, sidx::u64 *cap, sidx::u64 need, size_t elem, shockidx_result *res,
-               bool node = false);
-// device bytes held by the context's grow-only caches
-sidx::u64 workspace_bytes(const shockidx_ctx *c);
-// free the large caches (they regrow on demand); the tile status words go only with keep = 0
+// ---- the context's caches (sidx_build.cpp) -----------------------------------------------------
+// device bytes held by the context's caches (c->bufs)
+inline sidx::u64 workspace_bytes(const shockidx_ctx *c) { return c->bufs.bytes(); }
+// free the large caches when the total is over `keep` (they regrow on demand); the tile block
+// goes only with keep = 0, or when the rest is still over keep (BufSet::trim)
 void trim_workspace(shockidx_ctx *c, sidx::u64 keep);
 // trims the caches to the context's cap when a host-facing call returns
 struct TrimGuard {
@@ -218,7 +222,7 @@ struct SlabGeom {
   sidx::u32 seq = 0;  // the summary's build tag (shockidx_slab.seq)
 };
 int resolve_format(shockidx_ctx *c, const uint8_t *d_data, sidx::u64 n, int kind, int fmt, hipStream_t s, int *kfmt,
-                   shockidx_result *res, const int **gate = nullptr);
+                   Err res, const int **gate = nullptr);
 int respeculate(shockidx_ctx *c, const sidx::DevResult &dr, int *kfmt, shockidx_result *res);
 int run_index(shockidx_ctx *c, const uint8_t *d_data, sidx::u64 n, int kfmt, sidx::u64 *d_rows, sidx::u64 row_cap,
               hipStream_t s, sidx::DevResult *dr, shockidx_result *res, const SlabGeom *geom = nullptr,
@@ -233,7 +237,7 @@ int build_resident(shockidx_ctx *c, const uint8_t *d_data, sidx::u64 n, int kind
 // a row table the caller frees with free() / shockidx_free (2 MiB aligned when large)
 uint64_t *alloc_rows_out(size_t bytes);
 int rows_to_host(shockidx_ctx *c, const sidx::u64 *d_src, size_t bytes, uint8_t *dst, hipStream_t s,
-                 shockidx_result *res);
+                 Err res);
 int fetch_rows(shockidx_ctx *c, sidx::u64 count, hipStream_t s, uint64_t **rows, shockidx_result *res);
 // Host memory the GPU can DMA from directly (hipHostRegister'ed or hipHostMalloc'ed)
 bool host_pinned(const void *p, sidx::u64 n);
@@ -244,7 +248,7 @@ int stage_fd(shockidx_ctx *c, int fd, sidx::u64 off, sidx::u64 n, hipStream_t s,
 // (Linux returns at most 0x7ffff000 bytes per call; short reads and EINTR are retried).
 struct PreadFill {
   int fd;
-  shockidx_result *res;
+  Err res;
   CopyPool *pool;  // slices of each staging chunk are read by the pool's threads in parallel
   int operator()(uint8_t *dst, sidx::u64 off, size_t k) const;
 };
@@ -259,18 +263,18 @@ void pin_release(sidx::u64 b);
 // (shockidx_build_fd) or the temp .idx file (shockidx_create, pwrite at 16 * first row).
 struct RowSink {
   virtual ~RowSink() {}
-  virtual int put(const uint8_t *src, sidx::u64 first, sidx::u64 nrows, shockidx_result *res) = 0;
+  virtual int put(const uint8_t *src, sidx::u64 first, sidx::u64 nrows, Err res) = 0;
 };
 struct TableSink : RowSink {  // a malloc'ed table, grown as rows arrive (the caller frees it)
   uint8_t *out = nullptr;
   size_t cap = 0;
   explicit TableSink(sidx::u64 n);
   ~TableSink() override;
-  int put(const uint8_t *src, sidx::u64 first, sidx::u64 nrows, shockidx_result *res) override;
+  int put(const uint8_t *src, sidx::u64 first, sidx::u64 nrows, Err res) override;
 };
 struct FileSink : RowSink {  // the .idx temp file: rows are {u64 off, u64 len} LE (record.go:74-75)
   int fd = -1;
-  int put(const uint8_t *src, sidx::u64 first, sidx::u64 nrows, shockidx_result *res) override;
+  int put(const uint8_t *src, sidx::u64 first, sidx::u64 nrows, Err res) override;
 };
 // *done = false: not applicable, the caller runs the plain path
 int build_host_pipelined(shockidx_ctx *c, const void *data, sidx::u64 n, int kind, int fmt, uint64_t **rows,

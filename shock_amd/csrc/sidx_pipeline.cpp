@@ -66,7 +66,7 @@ TableSink::TableSink(u64 n) {
   if (!out) cap = 0;
 }
 TableSink::~TableSink() { free(out); }
-int TableSink::put(const uint8_t *src, u64 first, u64 nrows, shockidx_result *res) {
+int TableSink::put(const uint8_t *src, u64 first, u64 nrows, Err res) {
   const size_t need = (size_t)(first + nrows) * 16;
   if (need > cap) {
     size_t nc = cap ? cap : (64u << 20);
@@ -81,7 +81,7 @@ int TableSink::put(const uint8_t *src, u64 first, u64 nrows, shockidx_result *re
   memcpy(out + (size_t)first * 16, src, (size_t)nrows * 16);
   return 0;
 }
-int FileSink::put(const uint8_t *src, u64 first, u64 nrows, shockidx_result *res) {
+int FileSink::put(const uint8_t *src, u64 first, u64 nrows, Err res) {
   size_t left = (size_t)nrows * 16;
   off_t at = (off_t)(first * 16);
   while (left) {
@@ -103,12 +103,6 @@ namespace {
 // not a short table)
 const char *const SLAB_SEAM_MSG = "internal error: a slab's first row does not start where the previous slab's rows end";
 const char *const SLAB_END_MSG = "internal error: the rows do not end at the end of the file";
-
-void copy_error(shockidx_result *res, const shockidx_result &from, int code) {
-  memcpy(res->err, from.err, sizeof res->err);
-  res->err_len = from.err_len;
-  res->status = code;
-}
 
 // One arrival event per slab, recorded on the copy stream.  Destroyed only once the copy stream
 // has drained: declare it before whatever issues copies, so that it is destroyed after it.
@@ -147,8 +141,8 @@ int index_slab(shockidx_ctx *c, const SlabLayout &lay, u64 k, const uint8_t *d_s
   g.d_summary = c->d_small + SMALL_SLABSUM;
   int rc = run_index(c, d_slab, g.n, kfmt, c->d_rows + 2 * row_off, row_cap, c->stream, dr, r2, &g);
   if (grow && rc == 0 && dr->flags == RF_CAPACITY && dr->count > g.row_base &&
-      ensure_dev(c, (void **)&c->d_rows, &c->d_rows_cap, dr->count - g.row_base + 4096, 16, r2) == 0)
-    rc = run_index(c, d_slab, g.n, kfmt, c->d_rows, c->d_rows_cap, c->stream, dr, r2, &g);
+      c->d_rows.ensure(dr->count - g.row_base + 4096, r2) == 0)
+    rc = run_index(c, d_slab, g.n, kfmt, c->d_rows, c->d_rows.cap, c->stream, dr, r2, &g);
   return rc;
 }
 
@@ -246,7 +240,7 @@ struct Walk {
 // events outlive this object (SlabEvents is declared before it).
 class PageCacheSource {
  public:
-  PageCacheSource(shockidx_ctx *c, int fd, u64 base, u64 n, shockidx_result *res)
+  PageCacheSource(shockidx_ctx *c, int fd, u64 base, u64 n, Err res)
       : c_(c), res_(res), a0_(base & ~4095ull), lead_(base - a0_), mn_(lead_ + n),
         maplen_((size_t)((mn_ + 4095) & ~4095ull)), pinned_((mn_ + CH - 1) / CH, 0), fill_{fd, res, c->pool} {
     if (!getenv("SHOCKIDX_NO_MMAP_DMA")) {
@@ -269,7 +263,7 @@ class PageCacheSource {
   // node bytes [a, b) to device address dst: pinned chunks, else staging.  keep_from: the chunks
   // wholly before this node byte may be unpinned when the pin budget runs out
   int copy_range(uint8_t *dst, u64 a, u64 b, u64 keep_from) {
-    shockidx_result *res = res_;
+    const Err res = res_;
     a += lead_;  // (map coordinates from here: file offset a0 + x)
     b += lead_;
     keep_from += lead_;
@@ -328,7 +322,7 @@ class PageCacheSource {
     return true;
   }
   shockidx_ctx *c_;
-  shockidx_result *res_;
+  Err res_;
   const u64 a0_, lead_, mn_;  // the file from the page below base: node byte a is map[lead + a]
   const size_t maplen_;
   uint8_t *map_ = nullptr;
@@ -385,9 +379,9 @@ void index_slabs(Walk &w, WalkResult &o) {
     shockidx_result r2;
     reset_result(&r2);
     u64 row_base = 0;
-    const int rc = index_slab(c, lay, k, w.slab_ptr(k), o.kfmt, w.base, state, 0, c->d_rows_cap, true, &dr, &r2, &row_base);
+    const int rc = index_slab(c, lay, k, w.slab_ptr(k), o.kfmt, w.base, state, 0, c->d_rows.cap, true, &dr, &r2, &row_base);
     w.hand.release(k);  // (run_index waited for its kernels: the slot's bytes are no longer read)
-    if (rc < 0) return o.fail(set_msg(&o.cres, rc, r2.err));
+    if (rc < 0) return o.fail(forward_error(&o.cres, r2, rc));
     o.cres.kernel_ms += r2.kernel_ms;
     o.cres.index_ms += r2.index_ms;
     const SlabOutcome oc = classify(rc, dr, row_base, lay.last(k), lay.ring);
@@ -405,7 +399,7 @@ void index_slabs(Walk &w, WalkResult &o) {
 
 // The producer: the node's bytes onto the copy stream, each slab published once its bytes (and
 // halo) are all issued.  Ring: slab by slab into the slots; whole: 256 MiB at a time.
-int produce(Walk &w, PageCacheSource &src, shockidx_result *res) {
+int produce(Walk &w, PageCacheSource &src, Err res) {
   shockidx_ctx *c = w.c;
   const SlabLayout &lay = w.lay;
   const u64 K = lay.count();
@@ -437,7 +431,7 @@ int produce(Walk &w, PageCacheSource &src, shockidx_result *res) {
 
 // Both threads of a walk, until the index thread has ended and every copy has landed.  Returns
 // the producer's code; the walk's outcome is in o.
-int transfer(Walk &w, WalkResult &o, shockidx_result *res) {
+int transfer(Walk &w, WalkResult &o, Err res) {
   PageCacheSource src(w.c, w.fd, w.base, w.lay.n, res);
   std::thread ix(index_slabs, std::ref(w), std::ref(o));
   int prc = produce(w, src, res);
@@ -468,25 +462,15 @@ int one_pass_rest(Walk &w, WalkResult &o, shockidx_result *res, double t0) {
   shockidx_ctx *c = w.c;
   hipStream_t s = c->stream;
   const u64 r = o.cur.next_off, end = w.base + w.lay.n;
-  for (int i = 0; i < 2; ++i) {
-    (void)hipFree(c->d_slot[i]);
-    c->d_slot[i] = nullptr;
-  }
-  c->slot_cap = 0;
+  for (auto &slot : c->d_slot) slot.drop();
   if (one_pass_bytes(end - r) > dev_budget(c))
     return set_msg(res, SHOCKIDX_ENOMEM, "device memory: the node's one-pass fallback does not fit the device budget");
   shockidx_result r3;
   reset_result(&r3);
-  if (int rc = stage_fd(c, w.fd, r, end - r, s, &r3)) {
-    copy_error(res, r3, rc);
-    return rc;
-  }
+  if (int rc = stage_fd(c, w.fd, r, end - r, s, &r3)) return forward_error(res, r3, rc);
   const int sfmt = o.cur.total ? (o.kfmt == F_LINE ? SHOCKIDX_FMT_AUTO : o.kfmt) : w.fmt;
   const int rc = build_resident(c, c->d_in, end - r, w.kind, sfmt, s, &r3);
-  if (rc < 0) {
-    copy_error(res, r3, rc);
-    return rc;
-  }
+  if (rc < 0) return forward_error(res, r3, rc);
   const double td = now_ms();
   const u64 per = STAGE_BYTES / 16;
   for (u64 d = 0; d < r3.count;) {
@@ -503,7 +487,7 @@ int one_pass_rest(Walk &w, WalkResult &o, shockidx_result *res, double t0) {
   o.cres.kernel_ms += r3.kernel_ms;
   o.cres.index_ms += r3.index_ms;
   finish_walk(res, r3.format, o.cur.total, 4, o.cres, o.t_d2h + (now_ms() - td), t0);
-  copy_error(res, r3, r3.status);
+  forward_error(res, r3, r3.status);
   res->reruns = r3.reruns + 1;
   return rc;
 }
@@ -529,34 +513,28 @@ int prepare_buffers(shockidx_ctx *c, const SlabLayout &lay, shockidx_result *res
   hipStream_t s = c->stream;
   if (!c->s_copy) HIPCHK(hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking), "copy stream");
   for (int i = 0; i < 2; ++i)
-    if (!c->h_rows[i]) HIPCHK(hipHostMalloc((void **)&c->h_rows[i], STAGE_BYTES, 0), "hipHostMalloc(rows)");
+    if (!c->h_rows[i]) HIPCHK(hipHostMalloc(&c->h_rows[i], STAGE_BYTES, 0), "hipHostMalloc(rows)");
   const u64 SLOT = RING_FRONT + lay.S + PIPE_HALO + 64;  // (kept by the context, like its other caches, until a trim)
   if (lay.ring) {
-    if (c->slot_cap != SLOT) {
+    if (c->d_slot[0].cap != SLOT || c->d_slot[1].cap != SLOT) {
       // the caches of earlier (larger) builds go first: the node buffer of a one-pass build, rows
       trim_workspace(c, 0);
-      for (int i = 0; i < 2; ++i) HIPCHK(dev_malloc((void **)&c->d_slot[i], SLOT, true), "hipMalloc(slab slot)");
-      c->slot_cap = SLOT;
+      for (auto &slot : c->d_slot)
+        if (int rc = slot.exact(SLOT, res)) return rc;
     } else if (c->d_in) {
       (void)hipStreamSynchronize(s);
-      (void)hipFree(c->d_in);
-      c->d_in = nullptr;
-      c->d_in_cap = 0;
+      c->d_in.drop();
     }
   } else {
-    if (c->slot_cap) {  // (slots of an earlier build within a cap: not needed by this one)
+    if (c->d_slot[0] || c->d_slot[1]) {  // (slots of an earlier build within a cap: not needed by this one)
       (void)hipStreamSynchronize(s);
-      for (int i = 0; i < 2; ++i) {
-        (void)hipFree(c->d_slot[i]);
-        c->d_slot[i] = nullptr;
-      }
-      c->slot_cap = 0;
+      for (auto &slot : c->d_slot) slot.drop();
     }
-    if (int rc = ensure_dev(c, (void **)&c->d_in, &c->d_in_cap, lay.n + 64, 1, res, true)) return rc;
+    if (int rc = c->d_in.ensure(lay.n + 64, res)) return rc;
   }
   // per slab its rows' device capacity (reused slab after slab); a slab with more rows (records
   // or lines under 32 bytes on average) overflows it and is indexed again (index_slab)
-  return ensure_dev(c, (void **)&c->d_rows, &c->d_rows_cap, lay.S / 32 + 4096, 16, res);
+  return c->d_rows.ensure(lay.S / 32 + 4096, res);
 }
 
 // One walk over the file bytes [base, base + n) (the header comment of this file).
@@ -586,11 +564,10 @@ int build_fd_walk(shockidx_ctx *c, int fd, u64 n, int kind, int fmt, RowSink &si
   if (int prc = transfer(w, o, res)) return prc;
   switch (o.end) {
     case WalkEnd::Error:
-      copy_error(res, o.cres, o.err);
-      return o.err;
+      return forward_error(res, o.cres, o.err);
     case WalkEnd::NoFormat: {  // the detection's error, as the one-pass build reports it (no rows)
       const int code = o.cres.status ? o.cres.status : SHOCKIDX_EFORMAT;
-      copy_error(res, o.cres, code);
+      forward_error(res, o.cres, code);
       res->count = 0;
       res->total_ms = now_ms() - t0;
       return code;
@@ -676,7 +653,7 @@ int build_host_pipelined(shockidx_ctx *c, const void *data, u64 n, int kind, int
   const double t0 = now_ms();
   hipStream_t s = c->stream;
   if (!c->s_copy) HIPCHK(hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking), "copy stream");
-  if (int rc = ensure_dev(c, (void **)&c->d_in, &c->d_in_cap, n + 64, 1, res, true)) return rc;
+  if (int rc = c->d_in.ensure(n + 64, res)) return rc;
   const SlabLayout lay{n, PIPE_SLAB, false};
   const u64 K = lay.count();
   SlabEvents events(K, c->s_copy);
@@ -706,7 +683,7 @@ int build_host_pipelined(shockidx_ctx *c, const void *data, u64 n, int kind, int
   }
   if (kfmt != SHOCKIDX_FMT_FASTQ) return plain();
   const u64 rcap = n / 32 + 4096;
-  if (int rc = ensure_dev(c, (void **)&c->d_rows, &c->d_rows_cap, rcap, 16, res)) return rc;
+  if (int rc = c->d_rows.ensure(rcap, res)) return rc;
   size_t out_cap = (size_t)(n / 128 + 4096) * 16;
   struct FreeDel {
     void operator()(uint8_t *p) const { free(p); }
@@ -723,7 +700,7 @@ int build_host_pipelined(shockidx_ctx *c, const void *data, u64 n, int kind, int
     reset_result(&r2);
     u64 row_base = 0;
     const int rc = index_slab(c, lay, k, c->d_in + lay.lo(k), F_FASTQ, 0, state, cur.total, rcap - cur.total, false, &dr, &r2, &row_base);
-    if (rc < 0) return set_msg(res, rc, r2.err);
+    if (rc < 0) return forward_error(res, r2, rc);
     res->kernel_ms += r2.kernel_ms;
     res->index_ms += r2.index_ms;
     if (classify(rc, dr, row_base, lay.last(k), false) != SlabOutcome::Clean) {

@@ -84,44 +84,39 @@ std::string go_quote(const uint8_t *s, size_t n) {
 int subset_build(shockidx_ctx *c, const void *d_ids, uint64_t ids_len, const void *d_parent, uint64_t parent_count,
                  int64_t ilength, void *d_rows, uint64_t rows_cap, void *d_runs, uint64_t runs_cap, const void *d_data,
                  uint64_t data_len, void *d_out, uint64_t out_cap, shockidx_subset_result *res) {
-  sub_reset(res);
+  reset_result(res);
   if (!c || (!d_ids && ids_len) || ((uintptr_t)d_ids & 15) || (!d_parent && parent_count) ||
       (d_data && (((uintptr_t)d_data & 15) || ((uintptr_t)d_out & 15) || !d_runs)))
-    return sub_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+    return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
   const double t0 = now_ms();
-  SUBCHK(hipSetDevice(c->device), "hipSetDevice");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   hipStream_t s = c->stream;
   // 1. lines of the id text (subset.go:189-199, ReadLine = ReadBytes('\n')): the position of
   // every '\n' (sidx_id_lines) into the context's row workspace, then their count to the host;
   // the bytes after the last '\n' are dropped like ReadLine's EOF line
   const u64 nb = (ids_len + 1023) / 1024;
   size_t ltmp = 0;
-  SUBCHK(sidx_id_lines(nullptr, ids_len, nullptr, nullptr, nullptr, nullptr, &ltmp, s), "scan size");
+  HIPCHK(sidx_id_lines(nullptr, ids_len, nullptr, nullptr, nullptr, nullptr, &ltmp, s), "scan size");
   const u64 ends_bytes = (8 * (ids_len + 2) + 255) / 256 * 256;
   const u64 lbytes = ends_bytes + (4 * nb + 255) / 256 * 256 + (8 * nb + 255) / 256 * 256 + (ltmp + 255) / 256 * 256 + 256;
-  {
-    shockidx_result lr;
-    memset(&lr, 0, sizeof lr);
-    if (int rc = ensure_dev(c, (void **)&c->d_rows, &c->d_rows_cap, (lbytes + 15) / 16, 16, &lr))
-      return sub_msg(res, rc, lr.err);
-  }
+  if (int rc = c->d_rows.ensure((lbytes + 15) / 16, res)) return rc;
   u64 *ends = c->d_rows;
   u64 m = 0;
   {
-    Carver lc{(uint8_t *)c->d_rows + ends_bytes};
+    Carver lc{c->d_rows.as<uint8_t>() + ends_bytes};
     u32 *cnt = lc.take<u32>(nb);
     u64 *base = lc.take<u64>(nb);
     void *tmp = lc.take<uint8_t>(ltmp);
-    SUBCHK(hipEventRecord(c->ek0, s), "event");
-    SUBCHK(sidx_id_lines((const uint8_t *)d_ids, ids_len, cnt, base, ends, tmp, &ltmp, s), "id lines");
-    SUBCHK(hipEventRecord(c->ek1, s), "event");
+    HIPCHK(hipEventRecord(c->ek0, s), "event");
+    HIPCHK(sidx_id_lines((const uint8_t *)d_ids, ids_len, cnt, base, ends, tmp, &ltmp, s), "id lines");
+    HIPCHK(hipEventRecord(c->ek1, s), "event");
     u64 b_last = 0;
     u32 c_last = 0;
     if (nb) {
-      SUBCHK(hipMemcpyAsync(&b_last, base + nb - 1, 8, hipMemcpyDeviceToHost, s), "line count copy");
-      SUBCHK(hipMemcpyAsync(&c_last, cnt + nb - 1, 4, hipMemcpyDeviceToHost, s), "line count copy");
+      HIPCHK(hipMemcpyAsync(&b_last, base + nb - 1, 8, hipMemcpyDeviceToHost, s), "line count copy");
+      HIPCHK(hipMemcpyAsync(&c_last, cnt + nb - 1, 4, hipMemcpyDeviceToHost, s), "line count copy");
     }
-    SUBCHK(hipStreamSynchronize(s), "line count sync");
+    HIPCHK(hipStreamSynchronize(s), "line count sync");
     m = b_last + c_last;
     float lms = 0.f;
     (void)hipEventElapsedTime(&lms, c->ek0, c->ek1);
@@ -131,18 +126,14 @@ int subset_build(shockidx_ctx *c, const void *d_ids, uint64_t ids_len, const voi
   const bool gather = d_data != nullptr;
   const u64 gb = gather ? (m < runs_cap ? m : runs_cap) : 0;
   size_t scan_bytes = 0, gscan = 0;
-  SUBCHK(sidx_scan_flags(nullptr, nullptr, m ? m : 1, nullptr, &scan_bytes, s), "scan size");
+  HIPCHK(sidx_scan_flags(nullptr, nullptr, m ? m : 1, nullptr, &scan_bytes, s), "scan size");
   if (gather)
-    SUBCHK(sidx_gather(nullptr, 0, nullptr, gb, nullptr, nullptr, nullptr, nullptr, &gscan, nullptr, nullptr, 0, nullptr,
+    HIPCHK(sidx_gather(nullptr, 0, nullptr, gb, nullptr, nullptr, nullptr, nullptr, &gscan, nullptr, nullptr, 0, nullptr,
                        nullptr, s),
            "scan size");
   const u64 gblocks = gather ? (out_cap < data_len ? out_cap : data_len) / sidx::GATHER_BLOCK + 2 : 0;
   const u64 need = 8 * SC_ALLWORDS + 64 * (m + 8) + scan_bytes + 16 * (gb + 8) + gscan + 8 * gblocks + 4096;
-  {
-    shockidx_result wr;
-    memset(&wr, 0, sizeof wr);
-    if (int rc = ensure_dev(c, (void **)&c->d_sub, &c->d_sub_cap, need, 1, &wr)) return sub_msg(res, rc, wr.err);
-  }
+  if (int rc = c->d_sub.ensure(need, res)) return rc;
   Carver cv{c->d_sub};
   u64 *ctl = cv.take<u64>(SC_ALLWORDS);
   u32 *keep = cv.take<u32>(m + 1);
@@ -158,28 +149,28 @@ int subset_build(shockidx_ctx *c, const void *d_ids, uint64_t ids_len, const voi
   u64 *wfirst = cv.take<u64>(gblocks);
   u32 *startf = keep;  // reused after compaction
   u64 *runid = rank;
-  SUBCHK(hipEventRecord(c->ek0, s), "event");
-  SUBCHK(sidx_subset_init(ctl, 0, s), "init");
+  HIPCHK(hipEventRecord(c->ek0, s), "event");
+  HIPCHK(sidx_subset_init(ctl, 0, s), "init");
   if (m) {
-    SUBCHK(sidx_subset_parse((const uint8_t *)d_ids, ends, m, keep, val, st, s), "parse");
-    SUBCHK(sidx_scan_flags(keep, rank, m, scan_tmp, &scan_bytes, s), "scan");
-    SUBCHK(sidx_subset_compact(keep, rank, val, st, m, cval, cst, cline, ctl, s), "compact");
+    HIPCHK(sidx_subset_parse((const uint8_t *)d_ids, ends, m, keep, val, st, s), "parse");
+    HIPCHK(sidx_scan_flags(keep, rank, m, scan_tmp, &scan_bytes, s), "scan");
+    HIPCHK(sidx_subset_compact(keep, rank, val, st, m, cval, cst, cline, ctl, s), "compact");
   }
   // 3. per-id checks, row gather, run starts, Ke; 4. runs and oSize
-  SUBCHK(sidx_subset_check(cval, cst, m, ctl, (const u64 *)d_parent, parent_count, ilength, (u64 *)d_rows, rows_cap,
+  HIPCHK(sidx_subset_check(cval, cst, m, ctl, (const u64 *)d_parent, parent_count, ilength, (u64 *)d_rows, rows_cap,
                            startf, s),
          "check");
-  if (m) SUBCHK(sidx_scan_flags(startf, runid, m, scan_tmp, &scan_bytes, s), "scan");
-  SUBCHK(sidx_subset_runs((const u64 *)d_rows, startf, runid, m, ctl, (u64 *)d_runs, rows_cap, runs_cap, s), "runs");
-  SUBCHK(hipEventRecord(c->ek1, s), "event");
+  if (m) HIPCHK(sidx_scan_flags(startf, runid, m, scan_tmp, &scan_bytes, s), "scan");
+  HIPCHK(sidx_subset_runs((const u64 *)d_rows, startf, runid, m, ctl, (u64 *)d_runs, rows_cap, runs_cap, s), "runs");
+  HIPCHK(hipEventRecord(c->ek1, s), "event");
   // 5. the node's bytes, when asked for (skipped on the device after an error or a short capacity)
   if (gather)
-    SUBCHK(sidx_gather((const uint8_t *)d_data, data_len, (const u64 *)d_runs, gb, ctl, lens, outoff, gtmp, &gscan,
+    HIPCHK(sidx_gather((const uint8_t *)d_data, data_len, (const u64 *)d_runs, gb, ctl, lens, outoff, gtmp, &gscan,
                        wfirst, (uint8_t *)d_out, out_cap, c->ev0, c->ev1, s),
            "gather");
   u64 w[SC_ALLWORDS];
-  SUBCHK(hipMemcpyAsync(w, ctl, sizeof w, hipMemcpyDeviceToHost, s), "control copy");
-  SUBCHK(hipStreamSynchronize(s), "subset sync");
+  HIPCHK(hipMemcpyAsync(w, ctl, sizeof w, hipMemcpyDeviceToHost, s), "control copy");
+  HIPCHK(hipStreamSynchronize(s), "subset sync");
   for (int i = 0; i < SC_SLOTS; ++i) w[SC_SIZE] += w[SC_NWORDS + i];  // oSize (k_sub_runs' slots)
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, c->ek0, c->ek1);
@@ -194,12 +185,12 @@ int subset_build(shockidx_ctx *c, const void *d_ids, uint64_t ids_len, const voi
   res->total_ms = now_ms() - t0;
   if (w[SC_FLAGS] & 1) {
     res->count = Ke;
-    return sub_msg(res, SHOCKIDX_ESPACE, "row capacity too small");
+    return set_msg(res, SHOCKIDX_ESPACE, "row capacity too small");
   }
   if (w[SC_FLAGS] & 2) {
     res->count = Ke;
     res->runs = nstart;
-    return sub_msg(res, SHOCKIDX_ESPACE, "run capacity too small");
+    return set_msg(res, SHOCKIDX_ESPACE, "run capacity too small");
   }
   res->count = Ke;
   res->size = size;
@@ -207,8 +198,8 @@ int subset_build(shockidx_ctx *c, const void *d_ids, uint64_t ids_len, const voi
   // at an error the open run was never flushed
   res->runs = bad ? (nstart ? nstart - 1 : 0) : (size ? nstart : (nstart ? nstart - 1 : 0));
   if (gather && !bad) {
-    if (w[SC_FLAGS] & 8) return sub_msg(res, SHOCKIDX_EINVAL, "runs exceed the data");
-    if (w[SC_FLAGS] & 4) return sub_msg(res, SHOCKIDX_ESPACE, "output capacity too small");
+    if (w[SC_FLAGS] & 8) return set_msg(res, SHOCKIDX_EINVAL, "runs exceed the data");
+    if (w[SC_FLAGS] & 4) return set_msg(res, SHOCKIDX_ESPACE, "output capacity too small");
   }
   if (!bad) return SHOCKIDX_OK;
   // Go's error text for the first failing id
@@ -224,18 +215,18 @@ int subset_build(shockidx_ctx *c, const void *d_ids, uint64_t ids_len, const voi
     u64 li = 0, ln[2];
     if (int rc = d2h(c, &li, cline + r, res)) return rc;
     u64 e2[2] = {~0ull, 0};  // ends[li - 1], ends[li]: line li is [ends[li - 1] + 1, ends[li]]
-    SUBCHK(hipMemcpyAsync(li ? e2 : e2 + 1, c->d_rows + (li ? li - 1 : 0), li ? 16 : 8, hipMemcpyDeviceToHost, s),
+    HIPCHK(hipMemcpyAsync(li ? e2 : e2 + 1, c->d_rows + (li ? li - 1 : 0), li ? 16 : 8, hipMemcpyDeviceToHost, s),
            "line copy");
-    SUBCHK(hipStreamSynchronize(s), "sync");
+    HIPCHK(hipStreamSynchronize(s), "sync");
     ln[0] = e2[0] + 1;  // (li == 0: ~0 + 1 = 0)
     ln[1] = e2[1] + 1 - ln[0];
     const u64 k = ln[1] - 1 < 200 ? ln[1] - 1 : 200;  // enough for a 255-byte message
     uint8_t txt[200];
     if (k) {
-      SUBCHK(hipMemcpyAsync(txt, (const uint8_t *)d_ids + ln[0], k, hipMemcpyDeviceToHost, s), "text copy");
-      SUBCHK(hipStreamSynchronize(s), "sync");
+      HIPCHK(hipMemcpyAsync(txt, (const uint8_t *)d_ids + ln[0], k, hipMemcpyDeviceToHost, s), "text copy");
+      HIPCHK(hipStreamSynchronize(s), "sync");
     }
-    return sub_msg(res, SHOCKIDX_EFORMAT, "strconv.Atoi: parsing " + go_quote(txt, k) + ": " +
+    return set_msg(res, SHOCKIDX_EFORMAT, "strconv.Atoi: parsing " + go_quote(txt, k) + ": " +
                                               (code == SUB_SYNTAX ? "invalid syntax" : "value out of range"));
   }
   if (code == SUB_SORT)
@@ -246,7 +237,7 @@ int subset_build(shockidx_ctx *c, const void *d_ids, uint64_t ids_len, const voi
     snprintf(buf, sizeof buf, "Subset index: %lld does not exist in parent index file.", (long long)v);
   else
     snprintf(buf, sizeof buf, "Subset index could not read parent index file for part: %lld", (long long)v);
-  return sub_msg(res, SHOCKIDX_EFORMAT, buf);
+  return set_msg(res, SHOCKIDX_EFORMAT, buf);
 }
 
 }  // namespace
@@ -268,8 +259,8 @@ int shockidx_subset_node(shockidx_ctx *c, const void *d_ids, uint64_t ids_len, c
   shockidx_subset_result tmp;
   if (!d_data) {
     if (!res) res = &tmp;
-    sub_reset(res);
-    return sub_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+    reset_result(res);
+    return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
   }
   return subset_build(c, d_ids, ids_len, d_parent, parent_count, ilength, d_rows, rows_cap, d_runs, runs_cap, d_data,
                       data_len, d_out, out_cap, res ? res : &tmp);
@@ -279,43 +270,39 @@ int shockidx_subset_gather(shockidx_ctx *c, const void *d_data, uint64_t data_le
                            void *d_out, uint64_t out_cap, shockidx_subset_result *res) {
   shockidx_subset_result tmp;
   if (!res) res = &tmp;
-  sub_reset(res);
+  reset_result(res);
   if (!c || (!d_runs && nruns) || ((uintptr_t)d_data & 15) || ((uintptr_t)d_out & 15))
-    return sub_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+    return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
   const double t0 = now_ms();
-  SUBCHK(hipSetDevice(c->device), "hipSetDevice");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   hipStream_t s = c->stream;
   res->runs = nruns;
   if (!nruns) return SHOCKIDX_OK;
   size_t scan_bytes = 0;
-  SUBCHK(sidx_gather(nullptr, 0, nullptr, nruns, nullptr, nullptr, nullptr, nullptr, &scan_bytes, nullptr, nullptr, 0,
+  HIPCHK(sidx_gather(nullptr, 0, nullptr, nruns, nullptr, nullptr, nullptr, nullptr, &scan_bytes, nullptr, nullptr, 0,
                      nullptr, nullptr, s),
          "scan size");
   // runs are disjoint pieces of the parent file, so the output is at most data_len bytes
   const u64 max_blocks = (out_cap < data_len ? out_cap : data_len) / sidx::GATHER_BLOCK + 2;
   const u64 need = 8 * SC_ALLWORDS + 16 * (nruns + 16) + scan_bytes + 8 * max_blocks + 4096;
-  {
-    shockidx_result wr;
-    memset(&wr, 0, sizeof wr);
-    if (int rc = ensure_dev(c, (void **)&c->d_sub, &c->d_sub_cap, need, 1, &wr)) return sub_msg(res, rc, wr.err);
-  }
+  if (int rc = c->d_sub.ensure(need, res)) return rc;
   Carver cv{c->d_sub};
   u64 *ctl = cv.take<u64>(SC_ALLWORDS);
   u64 *lens = cv.take<u64>(nruns);
   u64 *outoff = cv.take<u64>(nruns);
   void *scan_tmp = cv.take<uint8_t>(scan_bytes);
   u64 *wfirst = cv.take<u64>(max_blocks);
-  SUBCHK(sidx_subset_init(ctl, nruns, s), "init");
-  SUBCHK(sidx_gather((const uint8_t *)d_data, data_len, (const u64 *)d_runs, nruns, ctl, lens, outoff, scan_tmp,
+  HIPCHK(sidx_subset_init(ctl, nruns, s), "init");
+  HIPCHK(sidx_gather((const uint8_t *)d_data, data_len, (const u64 *)d_runs, nruns, ctl, lens, outoff, scan_tmp,
                      &scan_bytes, wfirst, (uint8_t *)d_out, out_cap, c->ek0, c->ek1, s),
          "gather");
   u64 w[SC_NWORDS];
-  SUBCHK(hipMemcpyAsync(w, ctl, sizeof w, hipMemcpyDeviceToHost, s), "control copy");
-  SUBCHK(hipStreamSynchronize(s), "gather sync");
+  HIPCHK(hipMemcpyAsync(w, ctl, sizeof w, hipMemcpyDeviceToHost, s), "control copy");
+  HIPCHK(hipStreamSynchronize(s), "gather sync");
   res->size = w[SC_TOTAL];
   res->total_ms = now_ms() - t0;
-  if (w[SC_FLAGS] & 8) return sub_msg(res, SHOCKIDX_EINVAL, "runs exceed the data");
-  if (w[SC_FLAGS] & 4) return sub_msg(res, SHOCKIDX_ESPACE, "output capacity too small");
+  if (w[SC_FLAGS] & 8) return set_msg(res, SHOCKIDX_EINVAL, "runs exceed the data");
+  if (w[SC_FLAGS] & 4) return set_msg(res, SHOCKIDX_ESPACE, "output capacity too small");
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, c->ek0, c->ek1);
   res->kernel_ms = ms;
@@ -395,14 +382,14 @@ int parse_part(const char *part, i64 idx_length, i64 *a, i64 *b, const char **e)
 
 // row i of the device table (16 bytes D2H); a row past the table reads as `dflt`
 int read_row(shockidx_ctx *c, const void *d_rows, u64 nrows, u64 i, const u64 dflt[2], u64 out[2],
-             shockidx_subset_result *res) {
+             Err res) {
   if (i >= nrows) {
     out[0] = dflt[0];
     out[1] = dflt[1];
     return 0;
   }
-  SUBCHK(hipMemcpyAsync(out, (const u64 *)d_rows + 2 * i, 16, hipMemcpyDeviceToHost, c->stream), "row copy");
-  SUBCHK(hipStreamSynchronize(c->stream), "row sync");
+  HIPCHK(hipMemcpyAsync(out, (const u64 *)d_rows + 2 * i, 16, hipMemcpyDeviceToHost, c->stream), "row copy");
+  HIPCHK(hipStreamSynchronize(c->stream), "row sync");
   return 0;
 }
 
@@ -414,17 +401,17 @@ int shockidx_idx_part(shockidx_ctx *c, const void *d_rows, uint64_t nrows, const
                       int64_t *pos, int64_t *length, shockidx_subset_result *res) {
   shockidx_subset_result tmp;
   if (!res) res = &tmp;
-  sub_reset(res);
-  if (!c || !part || !pos || !length) return sub_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+  reset_result(res);
+  if (!c || !part || !pos || !length) return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
   *pos = 0;
   *length = 0;
   const double t0 = now_ms();
-  if (!d_rows) return sub_msg(res, SHOCKIDX_EFORMAT, E_IDX_NOFILE);  // index.go:70-74
-  SUBCHK(hipSetDevice(c->device), "hipSetDevice");
+  if (!d_rows) return set_msg(res, SHOCKIDX_EFORMAT, E_IDX_NOFILE);  // index.go:70-74
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   i64 a = 0, b = 0;
   const char *e = nullptr;
   const int kind = parse_part(part, idx_length, &a, &b, &e);
-  if (kind < 0) return sub_msg(res, SHOCKIDX_EFORMAT, e);
+  if (kind < 0) return set_msg(res, SHOCKIDX_EFORMAT, e);
   // fresh zeroed records (index.go:88,94,109): a read past the file leaves zeros
   static const u64 zero[2] = {0, 0};
   u64 sr[2], er[2];
@@ -446,25 +433,25 @@ int shockidx_idx_range(shockidx_ctx *c, const void *d_rows, uint64_t nrows, cons
                        void *d_recs, uint64_t recs_cap, shockidx_subset_result *res) {
   shockidx_subset_result tmp;
   if (!res) res = &tmp;
-  sub_reset(res);
-  if (!c || !part || (!d_recs && recs_cap)) return sub_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+  reset_result(res);
+  if (!c || !part || (!d_recs && recs_cap)) return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
   const double t0 = now_ms();
-  if (!d_rows) return sub_msg(res, SHOCKIDX_EFORMAT, E_IDX_NOFILE);  // index.go:122-126
-  SUBCHK(hipSetDevice(c->device), "hipSetDevice");
+  if (!d_rows) return set_msg(res, SHOCKIDX_EFORMAT, E_IDX_NOFILE);  // index.go:122-126
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   hipStream_t s = c->stream;
   i64 a = 0, b = 0;
   const char *e = nullptr;
   const int kind = parse_part(part, idx_length, &a, &b, &e);
-  if (kind < 0) return sub_msg(res, SHOCKIDX_EFORMAT, e);
+  if (kind < 0) return set_msg(res, SHOCKIDX_EFORMAT, e);
   const u64 a0 = (u64)(a - 1);
   if (kind == 0 || a == b) {  // one record (index.go:146-150, :185-191): rec starts zeroed
     static const u64 zero[2] = {0, 0};
     u64 r[2];
     if (int rc = read_row(c, d_rows, nrows, a0, zero, r, res)) return rc;
     res->count = 1;
-    if (recs_cap < 1) return sub_msg(res, SHOCKIDX_ESPACE, "record capacity too small");
-    SUBCHK(hipMemcpyAsync(d_recs, r, 16, hipMemcpyHostToDevice, s), "rec copy");
-    SUBCHK(hipStreamSynchronize(s), "rec sync");
+    if (recs_cap < 1) return set_msg(res, SHOCKIDX_ESPACE, "record capacity too small");
+    HIPCHK(hipMemcpyAsync(d_recs, r, 16, hipMemcpyHostToDevice, s), "rec copy");
+    HIPCHK(hipStreamSynchronize(s), "rec sync");
     res->total_ms = now_ms() - t0;
     return SHOCKIDX_OK;
   }
@@ -473,32 +460,25 @@ int shockidx_idx_range(shockidx_ctx *c, const void *d_rows, uint64_t nrows, cons
     return SHOCKIDX_OK;
   }
   const u64 nr = (u64)(b - a) + 1;
-  if (nr > (u64)INT32_MAX) return sub_msg(res, SHOCKIDX_EINVAL, "range too large for one call");
+  if (nr > (u64)INT32_MAX) return set_msg(res, SHOCKIDX_EINVAL, "range too large for one call");
   size_t scan_bytes = 0;
-  SUBCHK(sidx_scan_flags(nullptr, nullptr, nr, nullptr, &scan_bytes, s), "scan size");
+  HIPCHK(sidx_scan_flags(nullptr, nullptr, nr, nullptr, &scan_bytes, s), "scan size");
   const u64 need = 12 * (nr + 64) + scan_bytes + 4096;
-  {
-    shockidx_result wr;
-    memset(&wr, 0, sizeof wr);
-    if (int rc = ensure_dev(c, (void **)&c->d_sub, &c->d_sub_cap, need, 1, &wr)) return sub_msg(res, rc, wr.err);
-  }
+  if (int rc = c->d_sub.ensure(need, res)) return rc;
   Carver cv{c->d_sub};
   u32 *flags = cv.take<u32>(nr);
   u64 *id = cv.take<u64>(nr);
   void *scan_tmp = cv.take<uint8_t>(scan_bytes);
-  SUBCHK(hipEventRecord(c->ek0, s), "event");
-  SUBCHK(sidx_range_flags((const u64 *)d_rows, nrows, a0, nr, flags, s), "range flags");
-  SUBCHK(sidx_scan_flags(flags, id, nr, scan_tmp, &scan_bytes, s), "scan");
-  u64 lid = 0;
-  u32 lf = 0;
-  if (int rc = d2h(c, &lid, id + nr - 1, res)) return rc;
-  if (int rc = d2h(c, &lf, flags + nr - 1, res)) return rc;
-  const u64 nrec = lid + lf;
+  HIPCHK(hipEventRecord(c->ek0, s), "event");
+  HIPCHK(sidx_range_flags((const u64 *)d_rows, nrows, a0, nr, flags, s), "range flags");
+  HIPCHK(sidx_scan_flags(flags, id, nr, scan_tmp, &scan_bytes, s), "scan");
+  u64 nrec = 0;
+  if (int rc = scan_total(c, id, flags, nr, &nrec, res)) return rc;
   res->count = nrec;
-  if (nrec > recs_cap) return sub_msg(res, SHOCKIDX_ESPACE, "record capacity too small");
-  SUBCHK(sidx_range_emit((const u64 *)d_rows, nrows, a0, nr, flags, id, (u64 *)d_recs, s), "range emit");
-  SUBCHK(hipEventRecord(c->ek1, s), "event");
-  SUBCHK(hipStreamSynchronize(s), "range sync");
+  if (nrec > recs_cap) return set_msg(res, SHOCKIDX_ESPACE, "record capacity too small");
+  HIPCHK(sidx_range_emit((const u64 *)d_rows, nrows, a0, nr, flags, id, (u64 *)d_recs, s), "range emit");
+  HIPCHK(hipEventRecord(c->ek1, s), "event");
+  HIPCHK(hipStreamSynchronize(s), "range sync");
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, c->ek0, c->ek1);
   res->kernel_ms = ms;

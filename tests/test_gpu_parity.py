@@ -269,6 +269,98 @@ def test_workspace_trim_gpu(oracle_lib, monkeypatch):
             assert ctx.workspace_bytes() <= 1 << 20
 
 
+def test_every_cache_regrows_after_trim_gpu(oracle_lib, monkeypatch):
+    """One context, one call of every family that keeps a device cache (record and line build,
+    column index by both builds, chunkrecord, subset, fq2fa, anonymize over FASTA) on 256 KiB
+    inputs (16 tiles): they leave a workspace, trim(0) frees all of it, and every call made again
+    -- each cache regrown from nothing -- returns the same rows, bytes, counts and error text."""
+    from shock_amd import Context
+    import colref
+    size = 256 << 10
+    fq = gen.fq_fill(size)
+    fq_bad = gen.fastq_corrupt(random.Random(6), fq, "len_mismatch")
+    fa = gen.fasta(random.Random(7), 600)[:size]
+    tab = gen.sam(random.Random(8), 4000)[:size]
+    assert len(fq) == len(fa) == len(tab) == size and size <= len(fq_bad) < size + 16
+    parent, perr = oracle_lib.record_index(fq, "fastq")
+    assert perr is None
+    ids = b"".join(b"%d\n" % i for i in range(1, len(parent) + 1, 3))
+
+    def index(r):
+        rows = r.rows if r.rows is not None else np.zeros((0, 2), np.uint64)
+        return r.status, r.count, r.err, rows.tobytes()
+
+    def column(ctx, mode):
+        if mode:
+            monkeypatch.setenv("SHOCKIDX_COLUMN_MODE", mode)
+        else:
+            monkeypatch.delenv("SHOCKIDX_COLUMN_MODE", raising=False)
+        r = ctx.column_host(tab, 1)
+        monkeypatch.delenv("SHOCKIDX_COLUMN_MODE", raising=False)
+        return index(r) + (r.path,)
+
+    def chunk(ctx):
+        buf = ctx.alloc(size + 64)
+        buf.upload(fq)
+        rows = ctx.alloc(16 * ctx.chunkrecord_capacity(size, 40000))
+        r = ctx.chunkrecord_buffer(buf, size, rows, fmt="fastq", chunk=40000)
+        out = (r.status, r.count, r.err, rows.rows(r.count).tobytes())
+        buf.free()
+        rows.free()
+        return out
+
+    def subset(ctx):
+        r = ctx.subset_host(ids, parent, data=fq)
+        return r.status, r.count, r.runs, r.size, r.err, r.rows.tobytes(), r.run_rows.tobytes(), r.gathered
+
+    def filt(ctx, name, data):
+        r = ctx.filter_host(name, data)
+        return r.status, r.count, r.size, r.err, r.gathered
+
+    calls = {
+        "record": lambda ctx: index(ctx.build_host(fq, kind="record", fmt="fastq")),
+        "record_error": lambda ctx: index(ctx.build_host(fq_bad, kind="record", fmt="fastq")),
+        "line": lambda ctx: index(ctx.build_host(fq, kind="line")),
+        "column": lambda ctx: column(ctx, None),
+        "column_two": lambda ctx: column(ctx, "two"),
+        "chunkrecord": chunk,
+        "subset": subset,
+        "fq2fa": lambda ctx: filt(ctx, "fq2fa", fq),
+        "fq2fa_error": lambda ctx: filt(ctx, "fq2fa", fq_bad),
+        "anonymize_fasta": lambda ctx: filt(ctx, "anonymize", fa),
+    }
+    with Context(0) as ctx:
+        first = {name: call(ctx) for name, call in calls.items()}
+        assert ctx.workspace_bytes() > 0
+        ctx.trim(0)
+        assert ctx.workspace_bytes() == 0
+        again = {name: call(ctx) for name, call in calls.items()}
+    for name in calls:
+        assert again[name] == first[name], name
+    # and the first round is the reference's answer
+    exp, err = oracle_lib.record_index(fq_bad, "fastq")
+    assert err is not None and first["record_error"] == (1, len(exp), err, exp.tobytes())
+    assert first["record"] == (0, len(parent), None, parent.tobytes())
+    exp, err = oracle_lib.line_index(fq)
+    assert first["line"] == (0, len(exp), None, exp.tobytes())
+    want = colref.expected(tab, 1)
+    exp = np.array(want[1], dtype=np.uint64).reshape(-1, 2)
+    assert want[0] == "ok" and len(exp) > 1
+    assert first["column"] == (0, len(exp), None, exp.tobytes(), 1)
+    assert first["column_two"] == (0, len(exp), None, exp.tobytes(), 2)
+    exp, err = oracle_lib.chunkrecord(fq, "fastq", 40000)
+    assert err is None and first["chunkrecord"] == (0, len(exp), None, exp.tobytes())
+    rows, runs, osize, err = oracle_lib.subset(ids, parent, None)
+    gathered = b"".join(fq[int(o):int(o) + int(n)] for o, n in runs)
+    assert err is None
+    assert first["subset"] == (0, len(rows), len(runs), osize, None, rows.tobytes(), runs.tobytes(), gathered)
+    for name, data in (("fq2fa", fq), ("fq2fa_error", fq_bad), ("anonymize_fasta", fa)):
+        out, n, err = oracle_lib.filter_fastq(data, "anonymize" if name == "anonymize_fasta" else "fq2fa")
+        status, count, osize, gerr, got = first[name]
+        assert (name == "fq2fa_error") == (err is not None)
+        assert (status, count, gerr, got) == (1 if err else 0, n, err, out), name
+
+
 def test_format_speculation_gpu(gpu_ctx, oracle_lib):
     """AUTO builds speculate the context's last detected format (one host round trip): a file of
     another format (FASTA after FASTQ, SAM, undetectable bytes) is gated off on the device and
