@@ -44,7 +44,7 @@ extern "C" {
  *    SHOCKIDX_ESPACE (4 returned SHOCKIDX_EINVAL); whole-file builds check their own table's
  *    end invariants (SHOCKIDX_EINTERNAL instead of a short table).
  *    Added since without a version change (purely additive): shockidx_column_device,
- *    shockidx_column_fd */
+ *    shockidx_column_fd, shockidx_stream_filter_device */
 #define SHOCKIDX_ABI_VERSION 5
 
 /* index kinds = the registry keys served (index/index.go:21-28) */
@@ -356,6 +356,33 @@ int shockidx_idx_range(shockidx_ctx *ctx, const void *d_rows, uint64_t nrows, co
  * result->size = the bytes needed. */
 int shockidx_filter_device(shockidx_ctx *ctx, const char *filter, const void *d_data, uint64_t n, void *d_out,
                            uint64_t out_cap, shockidx_subset_result *result);
+
+/* ---- The sectioned stream: request.Streamer.Stream with a Filter --------------------------
+ * request/streamer.go:78-98 over sections of a node resident in HBM: the Streamer holds a list of
+ * SectionReaders and builds a new filter reader for each (s.Filter(sr), :86-87); for a subset node
+ * the list is every row Idx.Range returns (controller/node/single.go:397-400, 442-444, 457-460,
+ * 505-516).  d_secs: nsecs records {int64 pos, int64 len}, the layout shockidx_idx_range writes, so
+ * Range -> stream needs no host trip.  Sections may touch, overlap, repeat and come in any order.
+ * The result is that of shockidx_filter_device on section 0, 1, 2, ... alone, each over exactly the
+ * bytes [pos, pos + len), the outputs concatenated in list order: a section's end is end of file for
+ * its reader (a record whose quality line has no '\n' before it is dropped, in every section), the
+ * anonymize counter restarts at 1 and the format is detected again in every section
+ * (anonymize.go:28-56, multi.go:43-62; an empty section is "Invalid file type for filter"), and
+ * fq2fa over an empty section delivers nothing.  The stream stops after the first section whose
+ * status is not SHOCKIDX_OK (io.Copy's error, streamer.go:91-96): its delivered bytes are kept,
+ * nothing follows them, the call returns its status and text, and *err_section (optional) receives
+ * its index -- Streamer.ESection (:92-95) -- or -1.  result->count / size: records / bytes
+ * delivered over all sections.  A short out_cap returns SHOCKIDX_ESPACE with result->size = the
+ * bytes needed and nothing written.  A section with pos < 0, len < 0 or pos + len > data_len is
+ * SHOCKIDX_EINVAL and nothing is written: the reference's SectionReader would see a short read
+ * there, and a valid index never produces such a row.  filter NULL or "" is the Streamer without a
+ * Filter (:88-90): shockidx_subset_gather of the sections.  d_data and d_out 16-byte aligned.
+ * Sections of at most SHOCKIDX_STREAM_SMALL bytes (environment; default 1 MiB) that are FASTQ are
+ * indexed together, in a number of launches and host waits that does not grow with their number;
+ * the others go through the single-section filter one at a time. */
+int shockidx_stream_filter_device(shockidx_ctx *ctx, const char *filter, const void *d_data, uint64_t data_len,
+                                  const void *d_secs, uint64_t nsecs, void *d_out, uint64_t out_cap,
+                                  int64_t *err_section, shockidx_subset_result *result);
 
 /* ---- chunkrecord index -----------------------------------------
  * Indexers["chunkrecord"] (index/index.go:21-28, index/chunkrecord.go:41-99): rows of ~chunk

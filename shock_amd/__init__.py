@@ -14,5 +14,6 @@ See DESIGN.md and INTEGRATION.md.
 """
 from ._lib import ShockIdxError, lib  # noqa: F401
 from .core import Context, IndexResult, MultiContext  # noqa: F401
+from .stream import Streamer  # noqa: F401
 
-__all__ = ["Context", "IndexResult", "MultiContext", "ShockIdxError", "lib"]
+__all__ = ["Context", "IndexResult", "MultiContext", "ShockIdxError", "Streamer", "lib"]

@@ -409,6 +409,48 @@ class Context:
             d_out.free()
         return r
 
+    # -- the sectioned stream (request/streamer.go:78-98) -----------------------------------------
+    def stream_filter_device(self, name, d_data: int, data_len: int, d_secs: int, nsecs: int, d_out: int,
+                             out_cap: int) -> SubsetResult:
+        """Streamer.Stream with a Filter over nsecs sections {int64 pos, int64 len} (d_secs, the records
+        idx_range leaves on the device) of a node in HBM: every section through its own filter reader,
+        the outputs back to back (count = records, size = bytes out).  name None: no filter (the
+        gather).  r.err_section: the failing section (Streamer.ESection) or -1."""
+        r = L.SubsetResult()
+        es = ctypes.c_int64(-1)
+        rc = self._lib.shockidx_stream_filter_device(self._h, name.encode() if name else None, d_data, data_len, d_secs,
+                                                     nsecs, d_out, out_cap, ctypes.byref(es), ctypes.byref(r))
+        out = _sub_result(r, rc)
+        out.err_section = int(es.value)
+        return out
+
+    def stream_filter_host(self, name, data, sections) -> SubsetResult:
+        """Host-memory convenience: upload the node and the sections [(pos, len), ...], stream on the
+        device, download (r.gathered = the bytes delivered, also before an error)."""
+        data = bytes(data)
+        secs = np.ascontiguousarray(np.asarray(list(sections), dtype=np.int64).reshape(-1, 2))
+        d_in = self.alloc(len(data) + 64)
+        d_in.upload(data)
+        d_secs = self.alloc(16 * len(secs) + 64)
+        if len(secs):
+            d_secs.upload(secs.tobytes())
+        cap = 2 * int(secs[:, 1].clip(min=0).sum()) + 64 if len(secs) else 64
+        d_out = self.alloc(cap)
+        try:
+            r = self.stream_filter_device(name, d_in.ptr, len(data), d_secs.ptr, len(secs), d_out.ptr, cap)
+            if r.status == L.ESPACE:  # r.size holds the bytes needed
+                d_out.free()
+                cap = int(r.size) + 64
+                d_out = self.alloc(cap)
+                r = self.stream_filter_device(name, d_in.ptr, len(data), d_secs.ptr, len(secs), d_out.ptr, cap)
+            if r.status in (L.OK, L.EFORMAT):
+                r.gathered = d_out.download(r.size).tobytes() if r.size else b""
+        finally:
+            d_in.free()
+            d_secs.free()
+            d_out.free()
+        return r
+
     def detect(self, data):
         buf = np.frombuffer(bytes(data[:32768]), dtype=np.uint8)
         f = ctypes.c_int(0)
@@ -433,6 +475,7 @@ class SubsetResult:
     rows: np.ndarray | None = None
     run_rows: np.ndarray | None = None
     gathered: bytes | None = None
+    err_section: int = -1  # stream_filter_device: the failing section (Streamer.ESection)
 
     @property
     def ok(self) -> bool:

@@ -159,8 +159,9 @@ __global__ void k_slab_combine(const SlabSummary *all, int world, int rank, int 
 // k_detect: multi.go:43-62 over the zero-padded first 32768 bytes (fasta, fastq, sam)
 // ====================================================================================
 struct DetBuf {
-  const uint8_t *d;  // the zero-padded 32768-byte head, staged in LDS
-  __device__ __forceinline__ u32 at(u64 i) const { return d[i]; }
+  const uint8_t *d;  // the head, staged in LDS: m bytes, zeros from there to 32768 (not stored)
+  u32 m;
+  __device__ __forceinline__ u32 at(u64 i) const { return i < m ? (u32)d[i] : 0u; }
 };
 __device__ __forceinline__ bool dS(u32 c) { return !(c == '\t' || c == '\n' || c == '\f' || c == '\r' || c == ' '); }
 __device__ __forceinline__ bool dSST(u32 c) { return !(c == '\n' || c == '\f' || c == '\r'); }
@@ -174,12 +175,14 @@ template <class P>
 __device__ __forceinline__ u64 det_skip(const DetBuf &b, u64 i, P pred) {
   const u64 N = 32768;
   const int lane = threadIdx.x & 63;
-  for (u64 base = i; base < N; base += 64) {
+  u64 base = i;
+  for (; base < N && base < b.m; base += 64) {
     const u64 q = base + (u64)lane;
     const u64 m = __ballot(q < N && !pred(b.at(q)));
     if (m) return base + (u64)__builtin_ctzll(m);
   }
-  return N;
+  // only padding is left: every byte of it is zero
+  return (base < N && !pred(0u)) ? base : N;
 }
 __device__ __forceinline__ bool dLetDash(u32 c) { return dAlpha(c) || c == '-'; }
 
@@ -237,6 +240,23 @@ __device__ bool det_sam(const DetBuf &b) {
   return e > i && e < N && dNR(b.at(e));
 }
 
+// The three matchers over a staged head of m bytes, one per wave (side by side), each wave-wide;
+// called by the whole workgroup (at least three waves).  out[0]: the format, out[1]: the match mask.
+__device__ void det_match(const uint8_t *head, u32 m, int *out) {
+  __shared__ int part[3];
+  const DetBuf b{head, m};
+  if (threadIdx.x < 192) {
+    const int w = threadIdx.x >> 6;
+    const int r = w == 0 ? (det_fasta(b) ? 1 : 0) : w == 1 ? (det_fastq(b) ? 2 : 0) : (det_sam(b) ? 4 : 0);
+    if ((threadIdx.x & 63) == 0) part[w] = r;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const int mk = part[0] | part[1] | part[2];
+  out[0] = (mk & 1) ? F_FASTA : (mk & 2) ? F_FASTQ : (mk & 4) ? F_SAM : F_NONE;
+  out[1] = mk;
+}
+
 // The head is staged into LDS by the whole workgroup (16 B per lane, every load in flight at
 // once), then three waves run the three matchers against LDS.
 constexpr int DET_THREADS = 512;
@@ -255,19 +275,40 @@ __global__ __launch_bounds__(DET_THREADS) void k_detect(const uint8_t *data, u64
 #pragma unroll
   for (int k = 0; k < PER; ++k) *reinterpret_cast<uint4 *>(&head[(u64)(threadIdx.x + k * DET_THREADS) * 16]) = v[k];
   __syncthreads();
-  // the three matchers, one per wave (side by side), each wave-wide
-  __shared__ int part[3];
-  const DetBuf b{head};
-  if (threadIdx.x < 192) {
-    const int w = threadIdx.x >> 6;
-    const int r = w == 0 ? (det_fasta(b) ? 1 : 0) : w == 1 ? (det_fastq(b) ? 2 : 0) : (det_sam(b) ? 4 : 0);
-    if ((threadIdx.x & 63) == 0) part[w] = r;
+  det_match(head, 32768u, out);
+}
+
+// One workgroup per section {int64 pos, int64 len} of data: DetermineFormat over the section's
+// first min(len, 32768) bytes (multi.go:43-62 runs once per section reader).  pos is arbitrary, so
+// the head is staged from 16-byte aligned loads, byte by byte into LDS; the padding is not stored
+// (DetBuf::at).  out[s]: the format.  The caller has checked the sections against n.
+constexpr int DETB_THREADS = 256;
+__global__ __launch_bounds__(DETB_THREADS) void k_detect_sections(const uint8_t *data, u64 n, const i64 *secs,
+                                                                  u64 nsecs, int *out) {
+  __shared__ __align__(16) uint8_t head[32768];
+  __shared__ int res[2];
+  const u64 sidx = blockIdx.x;
+  if (sidx >= nsecs) return;
+  if (secs[2 * sidx] < 0 || secs[2 * sidx + 1] < 0 || (u64)secs[2 * sidx] > n ||
+      (u64)secs[2 * sidx + 1] > n - (u64)secs[2 * sidx]) {  // outside the node: the caller's error, nothing read
+    if (threadIdx.x == 0) out[sidx] = F_NONE;
+    return;
+  }
+  const u64 pos = (u64)secs[2 * sidx], len = (u64)secs[2 * sidx + 1];
+  const u32 m = (u32)(len < 32768 ? len : 32768);
+  const u64 lo = pos & ~15ull, hi = pos + m;
+  for (u64 a = lo + 16ull * threadIdx.x; a < hi; a += 16ull * DETB_THREADS) {
+    const uint4 v = (a + 16 <= n) ? load16(data + a) : load16_partial(data, a, n);
+    const u32 w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const u64 p = a + k;
+      if (p >= pos && p < hi) head[p - pos] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+    }
   }
   __syncthreads();
-  if (threadIdx.x != 0) return;
-  const int mk = part[0] | part[1] | part[2];
-  out[0] = (mk & 1) ? F_FASTA : (mk & 2) ? F_FASTQ : (mk & 4) ? F_SAM : F_NONE;
-  out[1] = mk;
+  det_match(head, m, res);
+  if (threadIdx.x == 0) out[sidx] = res[0];
 }
 
 // Whole-table check (SHOCKIDX_VERIFY builds, on in the GPU test suite): every row starts where
@@ -294,6 +335,13 @@ using namespace sidx;
 
 extern "C" hipError_t sidx_launch_detect(const uint8_t *d, u64 n, int *d_out, hipStream_t s) {
   hipLaunchKernelGGL(k_detect, dim3(1), dim3(DET_THREADS), 0, s, d, n, d_out);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t sidx_launch_detect_sections(const uint8_t *d, u64 n, const void *d_secs, u64 nsecs, int *d_out,
+                                                  hipStream_t s) {
+  if (nsecs) hipLaunchKernelGGL(k_detect_sections, dim3((u32)nsecs), dim3(DETB_THREADS), 0, s, d, n, (const i64 *)d_secs,
+                                nsecs, d_out);
   return hipGetLastError();
 }
 

@@ -24,20 +24,12 @@
 
 #include "sidx_common.hpp"
 #include "sidx_device.hpp"
+#include "sidx_fastq_read.hpp"
 #include "sidx_launch.hpp"
 
 namespace sidx {
 
 enum FilterKind : int { FILT_FQ2FA = 1, FILT_ANON_FQ = 2 };
-constexpr u64 NOLIM = ~0ull;
-
-struct GAcc {  // plain global-memory byte view for trim_space
-  const uint8_t *g;
-  __device__ __forceinline__ u32 byte(u64 p) const { return g[p]; }
-  __device__ __forceinline__ const uint8_t *ptr() const { return g; }
-  __device__ __forceinline__ u64 base() const { return 0; }
-};
-
 __device__ __forceinline__ u32 ndigits(u64 v) {  // compares, no divisions
   u32 d = 1;
   u64 p = 10;
@@ -51,8 +43,10 @@ __device__ __forceinline__ u32 ndigits(u64 v) {  // compares, no divisions
 
 // Per record: spans relative to the record start (id_lo, id_len, seq_lo, seq_len, qual_lo,
 // qual_len), the output length and Read's status for the checks the index did not make.
+// ord (nullable): each record's ordinal within its section, the sectioned stream's anonymize counter
+// (sidx_stream.hip: the reader, and with it the counter, restarts at every section); null: the flat index.
 __global__ __launch_bounds__(256) void k_fq_spans(const uint8_t *data, u64 n, const u64 *rows, u64 K, int kind,
-                                                  u32 *spans, u64 *outlen, u64 *firstbad) {
+                                                  u32 *spans, u64 *outlen, u64 *firstbad, const u32 *ord) {
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= K) return;
   {  // spans already placed from the tile pass (sidx_kernels.hip k_fq_spans_place): drop the mark
@@ -63,37 +57,8 @@ __global__ __launch_bounds__(256) void k_fq_spans(const uint8_t *data, u64 n, co
     }
   }
   const u64 off = rows[2 * i], len = rows[2 * i + 1], end = off + len;
-  // the first three '\n' of the record (the index guarantees they exist inside it)
-  u64 e0 = 0, e1 = 0, e2 = 0;
-  u32 found = 0;
-  // SIDX_SP_BATCH x 16 bytes per step, the loads issued together (one load per step cost a memory round
-  // trip per 16 bytes: 6.1 ms per 10 GiB section)
-#ifndef SIDX_SP_BATCH
-#define SIDX_SP_BATCH 4  // 16-byte loads issued together per step (4: 11.8 ms fq2fa, 8: 12.0, 16: 12.7)
-#endif
-  for (u64 b0 = off & ~15ull; b0 < end && found < 3; b0 += 16 * SIDX_SP_BATCH) {
-    uint4 v[SIDX_SP_BATCH];
-#pragma unroll
-    for (int k = 0; k < SIDX_SP_BATCH; ++k) {
-      const u64 b = b0 + 16 * (u64)k;
-      v[k] = (b + 16 <= n) ? load16(data + b) : (b < n ? load16_partial(data, b, n) : make_uint4(0, 0, 0, 0));
-    }
-#pragma unroll
-    for (int k = 0; k < SIDX_SP_BATCH; ++k) {
-      const u64 b = b0 + 16 * (u64)k;
-      u32 m = b < end ? eq16(v[k], '\n') : 0u;
-      if (b < off) m &= ~0u << (u32)(off - b);
-      while (m && found < 3) {
-        const u64 pos = b + (u64)__builtin_ctz(m);
-        if (pos >= end) break;
-        if (found == 0) e0 = pos;
-        else if (found == 1) e1 = pos;
-        else e2 = pos;
-        ++found;
-        m &= m - 1;
-      }
-    }
-  }
+  u64 e0 = 0, e1 = 0, e2 = 0;  // the first three '\n' of the record (the index guarantees they exist inside it)
+  first3_nl(data, n, off, end, e0, e1, e2);
   const GAcc a{data};
   u64 ilo, ihi, slo, shi, qlo, qhi;
   // the common record in one round of independent byte loads: every trimmed edge is a printable
@@ -123,7 +88,7 @@ __global__ __launch_bounds__(256) void k_fq_spans(const uint8_t *data, u64 n, co
   sp[2] = (u32)(slo - off); sp[3] = (u32)(shi - slo);
   sp[4] = (u32)(qlo - off); sp[5] = (u32)(qhi - qlo);
   outlen[i] = kind == FILT_FQ2FA ? (ihi - ilo) + (shi - slo) + 3
-                                 : (u64)ndigits(i + 1) + (shi - slo) + (qhi - qlo) + 6;
+                                 : (u64)ndigits(ord ? (u64)ord[i] + 1 : i + 1) + (shi - slo) + (qhi - qlo) + 6;
 }
 
 // ---- k_fq_write: output-centric (round 3) ----------------------------------------------------
@@ -282,10 +247,13 @@ __device__ __forceinline__ void fw_store(uint8_t *p, const uint4 v) {
   __builtin_nontemporal_store(x, reinterpret_cast<v4u *>(p));
 }
 
-template <int kind>  // the filter as a template argument: one code path per kernel
+// the filter as a template argument: one code path per kernel; ORD: the anonymize counter of record r
+// is ord[r] + 1 (its ordinal within its section, the sectioned stream) instead of r + 1
+template <int kind, bool ORD>
 __global__ __launch_bounds__(FW_THREADS) void k_fq_write(const uint8_t *data, u64 n, const u64 *rows, const u32 *spans,
                                                          const u64 *outoff, const u64 *wfirst, u64 K, u64 total,
-                                                         uint8_t *out) {
+                                                         uint8_t *out, const u32 *ord) {
+  auto counter = [&](u64 r) -> u64 { return ORD ? (u64)ord[r] + 1 : r + 1; };
   __shared__ u64 s_out[FW_RECS + 1];
   __shared__ u64 s_off[FW_RECS];
   __shared__ uint4 s_sp[FW_RECS];
@@ -306,9 +274,10 @@ __global__ __launch_bounds__(FW_THREADS) void k_fq_write(const uint8_t *data, u6
     s_out[i] = outoff[r0 + i];
     s_off[i] = rows[2 * (r0 + i)];
     s_sp[i] = fw_spans(spans, r0 + i, kind);
-    const u32 nd = ndigits(r0 + i + 1);
+    const u64 ctr = counter(r0 + i);
+    const u32 nd = ndigits(ctr);
     s_nd[i] = (uint8_t)nd;
-    s_dig[i] = kind == FILT_ANON_FQ ? fw_digits(r0 + i + 1, nd) : 0;
+    s_dig[i] = kind == FILT_ANON_FQ ? fw_digits(ctr, nd) : 0;
   }
   if (threadIdx.x == 0) s_out[nb] = r0 + nb < K ? outoff[r0 + nb] : total;
   __syncthreads();
@@ -339,7 +308,7 @@ __global__ __launch_bounds__(FW_THREADS) void k_fq_write(const uint8_t *data, u6
       }
 #endif
       for (u32 j = lo; j < nb && s_out[j] < oe; ++j) {
-        const u64 ctr = r0 + j + 1;
+        const u64 ctr = (ORD && s_nd[j] <= 8) ? 0 : counter(r0 + j);  // read only for more than 8 digits
         if (!fw_record(data, n, kind, s_off[j], s_sp[j], ctr, s_nd[j], s_dig[j], s_out[j], o, acc)) { slow = true; break; }
       }
     }
@@ -356,52 +325,10 @@ __global__ __launch_bounds__(FW_THREADS) void k_fq_write(const uint8_t *data, u6
     u64 r = lo;
     for (u64 p = o; p < oe; ++p) {
       while (r + 1 < K && outoff[r + 1] <= p) ++r;
-      out[p] = (uint8_t)fw_byte(data, kind, rows[2 * r], fw_spans(spans, r, kind), r + 1, ndigits(r + 1), p - outoff[r]);
+      const u64 ctr = counter(r);
+      out[p] = (uint8_t)fw_byte(data, kind, rows[2 * r], fw_spans(spans, r, kind), ctr, ndigits(ctr), p - outoff[r]);
     }
   }
-}
-
-// fastq.go:50-132 Reader.Read for the record at s (one wave; WaveAcc scans cooperatively).
-// Returns ST_OK / ST_END (no record: only blank lines or nothing left) or the error status.
-template <class A>
-__device__ u32 fastq_read_status(A &a, u64 s) {
-  u64 e0, e1, e2, e3;
-  u32 r;
-  if (s >= a.end) return ST_END;                // ReadBytes -> ("", EOF)  (:56-66)
-  r = a.find(C_NL, s, NOLIM, e0);
-  if (r == FR_NONE) return ST_FQ_TRUNC;         // non-empty id line at EOF (:68-72)
-  if (e0 == s) {                                // blank lines: skipped only up to EOF
-    u64 y, z;
-    r = a.find(C_NOTNL, s, NOLIM, y);
-    if (r == FR_NONE) return ST_END;
-    r = a.find(C_NL, y, NOLIM, z);
-    return r == FR_FOUND ? ST_FQ_EMPTYLINES : ST_FQ_TRUNC;  // (:76-78) / (:68-72)
-  }
-  if (a.byte(s) != '@') return ST_FQ_NOAT;      // :79-81
-  u64 ilo, ihi;
-  trim_space(a, s + 1, e0 + 1, ilo, ihi);
-  if (ihi == ilo) return ST_FQ_NOID;            // :83-87
-  r = a.find(C_NL, e0 + 1, NOLIM, e1);            // :89-95
-  if (r == FR_NONE) return ST_FQ_TRUNC;
-  u64 slo, shi;
-  trim_space(a, e0 + 1, e1 + 1, slo, shi);
-  if (shi == slo) return ST_FQ_EMPTYSEQ;        // :96-100
-  r = a.find(C_NL, e1 + 1, NOLIM, e2);            // :102-110
-  if (r == FR_NONE) return ST_FQ_TRUNC;
-  if (a.byte(e1 + 1) != '+') return ST_FQ_NOPLUS;
-  u64 plo, phi;
-  trim_space(a, e1 + 1, e2 + 1, plo, phi);      // :111-115
-  if (phi - plo > 1) {
-    if (ihi - ilo != phi - plo - 1) return ST_FQ_IDMISMATCH;
-    for (u64 k = 0; k < ihi - ilo; ++k)
-      if (a.byte(ilo + k) != a.byte(plo + 1 + k)) return ST_FQ_IDMISMATCH;
-  }
-  r = a.find(C_NL, e2 + 1, NOLIM, e3);            // :117-126, EOF tolerated
-  const u64 qend = (r == FR_FOUND) ? e3 + 1 : a.end;
-  u64 qlo, qhi;
-  trim_space(a, e2 + 1, qend, qlo, qhi);
-  if (shi - slo != qhi - qlo) return ST_FQ_LENMISMATCH;
-  return ST_OK;
 }
 
 __global__ void k_fq_read_status(const uint8_t *data, u64 n, u64 s, u32 *out) {
@@ -865,25 +792,26 @@ __global__ __launch_bounds__(256) void k_sam_anon_write(const uint8_t *d, const 
 using namespace sidx;
 
 extern "C" hipError_t sidx_filter_spans(const uint8_t *data, u64 n, const u64 *rows, u64 K, int kind, u32 *spans,
-                                        u64 *outlen, u64 *firstbad, hipStream_t s) {
+                                        u64 *outlen, u64 *firstbad, const u32 *ord, hipStream_t s) {
   if (K) hipLaunchKernelGGL(k_fq_spans, dim3((u32)((K + 255) / 256)), dim3(256), 0, s, data, n, rows, K, kind, spans,
-                            outlen, firstbad);
+                            outlen, firstbad, ord);
   return hipGetLastError();
 }
 
 // wfirst: total / FW_BLOCK + 1 words (the first record of every output block)
 extern "C" hipError_t sidx_filter_write(const uint8_t *data, u64 n, const u64 *rows, const u32 *spans, const u64 *outlen,
                                         const u64 *outoff, u64 K, u64 total, int kind, u64 *wfirst, uint8_t *out,
-                                        hipStream_t s) {
+                                        const u32 *ord, hipStream_t s) {
   if (!K || !total) return hipSuccess;
   const u64 nblocks = (total + FW_BLOCK - 1) / FW_BLOCK;
   hipLaunchKernelGGL(k_fw_plan, dim3((u32)((K + 255) / 256)), dim3(256), 0, s, outoff, outlen, K, nblocks, wfirst);
-  if (kind == FILT_FQ2FA)
-    hipLaunchKernelGGL(k_fq_write<FILT_FQ2FA>, dim3((u32)nblocks), dim3(FW_THREADS), 0, s, data, n, rows, spans, outoff,
-                       wfirst, K, total, out);
-  else
-    hipLaunchKernelGGL(k_fq_write<FILT_ANON_FQ>, dim3((u32)nblocks), dim3(FW_THREADS), 0, s, data, n, rows, spans, outoff,
-                       wfirst, K, total, out);
+#define SIDX_FW_LAUNCH(KIND, ORD)                                                                                  \
+  hipLaunchKernelGGL((k_fq_write<KIND, ORD>), dim3((u32)nblocks), dim3(FW_THREADS), 0, s, data, n, rows, spans, outoff, \
+                     wfirst, K, total, out, ord)
+  if (kind == FILT_FQ2FA) SIDX_FW_LAUNCH(FILT_FQ2FA, false);  // fq2fa writes no counter
+  else if (ord) SIDX_FW_LAUNCH(FILT_ANON_FQ, true);
+  else SIDX_FW_LAUNCH(FILT_ANON_FQ, false);
+#undef SIDX_FW_LAUNCH
   return hipGetLastError();
 }
 extern "C" u64 sidx_filter_block() { return FW_BLOCK; }

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/shockidx.h"
 #include "sidx_common.hpp"
@@ -28,8 +29,9 @@ int scan_lengths(shockidx_ctx *c, const u64 *len, u64 *off, u64 K, void *tmp, si
 
 // anonymize over a FASTA or SAM section (anonymize.go:28-56 through multi.Reader): the stream
 // Read + Format deliver (sidx_filter.hip), count / size delivered, Read's error text.
+// size_only: see filter_section.
 int anonymize_other(shockidx_ctx *c, const uint8_t *dd, u64 n, int kfmt, uint8_t *d_out, u64 out_cap,
-                    shockidx_subset_result *res, double t0) {
+                    shockidx_subset_result *res, double t0, bool size_only) {
   hipStream_t s = c->stream;
   const bool fasta = kfmt == SHOCKIDX_FMT_FASTA;
   u64 K = 0;            // FASTA: boundaries (sequences before the EOF one); SAM: lines
@@ -110,6 +112,17 @@ int anonymize_other(shockidx_ctx *c, const uint8_t *dd, u64 n, int kfmt, uint8_t
   if (int rc = scan_lengths(c, outlen, outoff, Ke, scan_tmp, &tb, &total, res)) return rc;
   res->size = total;
   res->count = fasta ? Ke : 0;
+  if (size_only && !fasta) {  // SAM counts its lines as it writes them: the delivered ones (outlen != 0) here
+    std::vector<u64> ol(Ke);
+    if (Ke) HIPCHK(hipMemcpyAsync(ol.data(), outlen, 8 * Ke, hipMemcpyDeviceToHost, s), "length copy");
+    HIPCHK(hipStreamSynchronize(s), "length sync");
+    for (u64 v : ol) res->count += v != 0;
+  }
+  if (size_only) {
+    res->total_ms = now_ms() - t0;
+    return err ? set_msg(res, SHOCKIDX_EFORMAT, fasta ? "Invalid fasta entry" : "sam alignment fields less than 11")
+               : SHOCKIDX_OK;
+  }
   if (total > out_cap) return set_msg(res, SHOCKIDX_ESPACE, "output capacity too small");
   if (fasta) HIPCHK(sidx_fa_anon_write(dd, n, span, outoff, Ke, d_out, s), "anonymize write");
   else HIPCHK(sidx_sam_anon_write(dd, span, outlen, outoff, Ke, d_out, small + 2, s), "anonymize write");
@@ -130,28 +143,26 @@ int anonymize_other(shockidx_ctx *c, const uint8_t *dd, u64 n, int kfmt, uint8_t
 
 }  // namespace
 
-// ---- Download filters on device: fq2fa / anonymize (node/filter/) --------------------------
-extern "C" {
+namespace sidx_host {
 
-int shockidx_filter_device(shockidx_ctx *c, const char *filter, const void *d_data, uint64_t n, void *d_out,
-                           uint64_t out_cap, shockidx_subset_result *res) {
-  shockidx_subset_result tmp;
-  if (!res) res = &tmp;
-  reset_result(res);
-  if (!c || !filter || (!d_data && n) || ((uintptr_t)d_data & 15) || (!d_out && out_cap))
-    return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
-  int kind = 0;  // filter.go:13-16
-  if (!strcmp(filter, "fq2fa")) kind = 1;
-  else if (!strcmp(filter, "anonymize")) kind = 2;
-  else return set_msg(res, SHOCKIDX_EINVAL, "unknown filter");
+int filter_kind(const char *filter) {  // filter.go:13-16
+  if (!strcmp(filter, "fq2fa")) return 1;
+  if (!strcmp(filter, "anonymize")) return 2;
+  return 0;
+}
+
+// One section through its filter (res reset by the caller).  size_only: nothing is written and
+// out_cap is not looked at -- the section's own status (OK or EFORMAT with Go's text) comes back
+// with count / size = what a write would deliver (the sectioned stream sizes its output first).
+int filter_section(shockidx_ctx *c, int kind, const uint8_t *dd, u64 n, void *d_out, u64 out_cap,
+                   shockidx_subset_result *res, bool size_only) {
   const double t0 = now_ms();
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
   hipStream_t s = c->stream;
-  const uint8_t *dd = (const uint8_t *)d_data;
   if (kind == 2) {  // anonymize reads through multi.Reader: DetermineFormat first (multi.go:43-62)
     int kfmt = 0;
     if (int rc = resolve_format(c, dd, n, SHOCKIDX_RECORD, SHOCKIDX_FMT_AUTO, s, &kfmt, res)) return rc;
-    if (kfmt != SHOCKIDX_FMT_FASTQ) return anonymize_other(c, dd, n, kfmt, (uint8_t *)d_out, out_cap, res, t0);
+    if (kfmt != SHOCKIDX_FMT_FASTQ) return anonymize_other(c, dd, n, kfmt, (uint8_t *)d_out, out_cap, res, t0, size_only);
   }
   // the record index (GetReadOffset) gives the record boundaries up to its first error; its tile
   // pass keeps every record's line ends for the spans
@@ -182,7 +193,7 @@ int shockidx_filter_device(shockidx_ctx *c, const char *filter, const void *d_da
     HIPCHK(hipMemsetAsync(outlen, 0, 8 * K, s), "memset");
     HIPCHK(sidx_launch_fq_spans_place(&c->last_p, spans, outlen, K, kind, s), "spans place");
   }
-  HIPCHK(sidx_filter_spans(dd, n, c->d_rows, K, kind, spans, outlen, small, s), "filter spans");
+  HIPCHK(sidx_filter_spans(dd, n, c->d_rows, K, kind, spans, outlen, small, nullptr, s), "filter spans");
   u64 firstbad = ~0ull;
   if (int rc = d2h(c, &firstbad, small, res)) return rc;
   // Read()'s first failing record: one the index accepted but Read rejects (a blank-looking ID
@@ -212,10 +223,13 @@ int shockidx_filter_device(shockidx_ctx *c, const char *filter, const void *d_da
   if (int rc = scan_lengths(c, outlen, outoff, Ke, scan_tmp, &scan_bytes, &total, res)) return rc;
   res->count = Ke;
   res->size = total;
-  if (total > out_cap) return set_msg(res, SHOCKIDX_ESPACE, "output capacity too small");
-  if (total / sidx_filter_block() + 1 > nwf) return set_msg(res, SHOCKIDX_EINTERNAL, "internal error: filter plan size");
-  HIPCHK(sidx_filter_write(dd, n, c->d_rows, spans, outlen, outoff, Ke, total, kind, wfirst, (uint8_t *)d_out, s),
-         "filter write");
+  if (!size_only) {
+    if (total > out_cap) return set_msg(res, SHOCKIDX_ESPACE, "output capacity too small");
+    if (total / sidx_filter_block() + 1 > nwf) return set_msg(res, SHOCKIDX_EINTERNAL, "internal error: filter plan size");
+    HIPCHK(sidx_filter_write(dd, n, c->d_rows, spans, outlen, outoff, Ke, total, kind, wfirst, (uint8_t *)d_out, nullptr,
+                             s),
+           "filter write");
+  }
   HIPCHK(hipEventRecord(c->ek1, s), "event");
   HIPCHK(hipStreamSynchronize(s), "filter sync");
   float ms = 0.f;
@@ -225,6 +239,23 @@ int shockidx_filter_device(shockidx_ctx *c, const char *filter, const void *d_da
   if (code == ST_END) return SHOCKIDX_OK;
   const char *m = status_message(code);
   return set_msg(res, SHOCKIDX_EFORMAT, m ? m : "internal error: filter status");
+}
+
+}  // namespace sidx_host
+
+// ---- Download filters on device: fq2fa / anonymize (node/filter/) --------------------------
+extern "C" {
+
+int shockidx_filter_device(shockidx_ctx *c, const char *filter, const void *d_data, uint64_t n, void *d_out,
+                           uint64_t out_cap, shockidx_subset_result *res) {
+  shockidx_subset_result tmp;
+  if (!res) res = &tmp;
+  reset_result(res);
+  if (!c || !filter || (!d_data && n) || ((uintptr_t)d_data & 15) || (!d_out && out_cap))
+    return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+  const int kind = filter_kind(filter);
+  if (!kind) return set_msg(res, SHOCKIDX_EINVAL, "unknown filter");
+  return filter_section(c, kind, (const uint8_t *)d_data, n, d_out, out_cap, res, false);
 }
 
 }  // extern "C"

@@ -121,6 +121,7 @@ struct shockidx_ctx {
   u32 cr_grid = 0;                 //   k_cr_verify persistent grid
   Buf<uint8_t> d_cola{bufs};       // column index: the line table, then the cut offsets (bytes)
   Buf<uint8_t> d_colb{bufs};       //   flags, ranks, key spans, scan workspace (bytes)
+  Buf<uint8_t> d_sec{bufs};        // sectioned stream: one large section staged 16-byte aligned, and its output (bytes)
   hipStream_t s_copy = nullptr;    // slab-pipelined host builds: the H2D stream
   uint8_t *h_rows[2] = {nullptr, nullptr};  // slab-pipelined fd builds: pinned row staging (D2H)
   // download filters over FASTQ: the tile pass keeps each record's line ends (k_fq_tiles<true>)
@@ -232,6 +233,14 @@ bool verify_rows();
 int translate(shockidx_ctx *c, const sidx::DevResult &dr, const uint8_t *d_data, hipStream_t s, shockidx_result *res);
 int build_resident(shockidx_ctx *c, const uint8_t *d_data, sidx::u64 n, int kind, int fmt, hipStream_t s,
                    shockidx_result *res);
+
+// ---- the download filters (sidx_filter_api.cpp) ------------------------------------------------
+// filter.go:13-16: 1 fq2fa, 2 anonymize, 0 unknown
+int filter_kind(const char *filter);
+// one section (16-byte aligned, n bytes) through its filter; size_only: nothing written, out_cap
+// ignored, the section's own status with the count / size a write would deliver
+int filter_section(shockidx_ctx *c, int kind, const uint8_t *dd, sidx::u64 n, void *d_out, sidx::u64 out_cap,
+                   shockidx_subset_result *res, bool size_only);
 
 // ---- staging and copy-out (sidx_build.cpp) ---------------------------------------------------
 // a row table the caller frees with free() / shockidx_free (2 MiB aligned when large)

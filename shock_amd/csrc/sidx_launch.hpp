@@ -13,6 +13,9 @@
 extern "C" {
 
 hipError_t sidx_launch_detect(const uint8_t *d, sidx::u64 n, int *d_out, hipStream_t s);
+// DetermineFormat per section {int64 pos, int64 len} of d (sections checked against n): d_out[s] = the format
+hipError_t sidx_launch_detect_sections(const uint8_t *d, sidx::u64 n, const void *d_secs, sidx::u64 nsecs, int *d_out,
+    hipStream_t s);
 // one slab's build on the given path (the two-pass build's format: p->gate_fmt)
 hipError_t sidx_launch_tiles(sidx::TilePass pass, const sidx::SlabParams *p, sidx::DevResult *d_res, hipStream_t s,
     hipEvent_t ek0, hipEvent_t ek1);
@@ -94,12 +97,22 @@ hipError_t sidx_subset_runs(const sidx::u64 *rows, const sidx::u32 *startf, cons
 hipError_t sidx_launch_fq_spans_place(const sidx::SlabParams *pp, sidx::u32 *spans, sidx::u64 *outlen, sidx::u64 K,
     int kind, hipStream_t s);
 hipError_t sidx_filter_spans(const uint8_t *data, sidx::u64 n, const sidx::u64 *rows, sidx::u64 K, int kind,
-    sidx::u32 *spans, sidx::u64 *outlen, sidx::u64 *firstbad, hipStream_t s);
+    sidx::u32 *spans, sidx::u64 *outlen, sidx::u64 *firstbad, const sidx::u32 *ord, hipStream_t s);
 hipError_t sidx_filter_write(const uint8_t *data, sidx::u64 n, const sidx::u64 *rows, const sidx::u32 *spans,
     const sidx::u64 *outlen, const sidx::u64 *outoff, sidx::u64 K, sidx::u64 total, int kind, sidx::u64 *wfirst,
-    uint8_t *out, hipStream_t s);
+    uint8_t *out, const sidx::u32 *ord, hipStream_t s);
 sidx::u64 sidx_filter_block();
 hipError_t sidx_filter_read_status(const uint8_t *data, sidx::u64 n, sidx::u64 start, sidx::u32 *out,
+    hipStream_t s);
+// the sectioned stream (sidx_stream.hip; control words: sidx_stream.hpp): range check and the sections
+// the segmented path leaves to the single-section filter; a batch's records per section; after the
+// scan of cnt into base, the batch's rows / ordinals / sections and ctl[SS_KEY], ctl[SS_KE]
+hipError_t sidx_stream_classify(const void *d_secs, sidx::u64 nsecs, sidx::u64 n, const int *fmt, sidx::u64 small,
+    sidx::u64 *ctl, sidx::u64 *others, hipStream_t s);
+hipError_t sidx_stream_count(const uint8_t *data, sidx::u64 n, const void *d_secs, sidx::u64 S, sidx::u64 *cnt,
+    hipStream_t s);
+hipError_t sidx_stream_index(const uint8_t *data, sidx::u64 n, const void *d_secs, sidx::u64 S, const sidx::u64 *cnt,
+    const sidx::u64 *base, sidx::u64 K, sidx::u64 *rows, sidx::u32 *ord, sidx::u32 *rsec, sidx::u64 *ctl,
     hipStream_t s);
 hipError_t sidx_range_flags(const sidx::u64 *rows, sidx::u64 nrows, sidx::u64 a0, sidx::u64 nr, sidx::u32 *flags,
     hipStream_t s);
