@@ -24,6 +24,10 @@
  *   shockidx_chunkrecord_subset_device  chunkRecord.Create for subset nodes (chunkrecord.go:100-228)
  *                          with fastq.go:216-243 / fasta.go:143-173 SeekChunk
  *   shockidx_column_device / shockidx_column_fd  CreateColumnIndex: index/column.go:33-130
+ *   shockidx_download_plan the section list of a ?download&index=X&part=a&part=b... request, the
+ *                          s.R = append(...) loops of controller/node/single.go:372-483 (Idx.Part /
+ *                          Idx.Range per part, the subset node's chunkrecord branch :401-425) and
+ *                          the virtual size index, index/virtual.go:50-80
  *
  * Semantics: results are bit-identical to the Go path on the same bytes, including the
  * exact error strings (fastq.go:156-207, fasta.go:120, errors.go:20) and the record count
@@ -44,7 +48,7 @@ extern "C" {
  *    SHOCKIDX_ESPACE (4 returned SHOCKIDX_EINVAL); whole-file builds check their own table's
  *    end invariants (SHOCKIDX_EINTERNAL instead of a short table).
  *    Added since without a version change (purely additive): shockidx_column_device,
- *    shockidx_column_fd, shockidx_stream_filter_device */
+ *    shockidx_column_fd, shockidx_stream_filter_device, shockidx_download_plan */
 #define SHOCKIDX_ABI_VERSION 5
 
 /* index kinds = the registry keys served (index/index.go:21-28) */
@@ -383,6 +387,50 @@ int shockidx_filter_device(shockidx_ctx *ctx, const char *filter, const void *d_
 int shockidx_stream_filter_device(shockidx_ctx *ctx, const char *filter, const void *d_data, uint64_t data_len,
                                   const void *d_secs, uint64_t nsecs, void *d_out, uint64_t out_cap,
                                   int64_t *err_section, shockidx_subset_result *result);
+
+/* ---- The download plan: all parts of an index download in one call -------------------------
+ * controller/node/single.go:372-483 builds the Streamer's section list (s.R) part by part: a request
+ * may repeat part= any number of times, every part is one Idx.Part section or the records of one
+ * Idx.Range, appended in order, and the request fails at the first part in error (nothing is
+ * streamed).  This call does that for the whole list at once, over indexes resident in HBM, in a
+ * number of launches and host waits that does not grow with nparts.  d_secs receives result->count
+ * records {int64 pos, int64 len} -- what the reference appends to s.R, in its order, the layout
+ * shockidx_idx_range writes and shockidx_stream_filter_device reads -- and result->size is Go's
+ * `size` (single.go:369, the int64 sum of the lengths, wrapping).  Modes: */
+enum shockidx_plan_mode {
+  SHOCKIDX_PLAN_PART = 0,        /* idx.Part per part: single.go:461-475 (non-subset index of a file) */
+  SHOCKIDX_PLAN_RANGE = 1,       /* idx.Range per part: single.go:433-460, 505-516 (subset index / subset node) */
+  SHOCKIDX_PLAN_CHUNK_RANGE = 2, /* subset node + chunkrecord: single.go:401-425 (Range, then Range per chunk run) */
+  SHOCKIDX_PLAN_SIZE = 3         /* the virtual size index: virtual.go:50-80 with single.go:357-366's chunk_size */
+};
+/* PART: one section per part with Idx.Part's arithmetic (index.go:86-114); a row past the table
+ * reads as zeros.  RANGE: the sections of part 0, then part 1, ...; each part's are Idx.Range's
+ * maximal runs (curLen == nextPos - curPos, index.go:152-177), "N" and "N-N" one record, b < a none;
+ * a row past the table reads as the last row read in that part's walk (zeros when its first row is
+ * past the table); sections of different parts never merge, also when they touch, overlap or
+ * repeat.  CHUNK_RANGE: RANGE over d_rows, the "matrix" index of shockidx_chunkrecord_subset_device
+ * (rows (16 * first row, 16 * rows)); every record (c0, c1) it yields, in order, becomes
+ * start = c0/16 + 1, stop = (start-1) + c1/16 (int64, truncating, wrapping) and the sections are
+ * Idx.Range("start-stop") over d_rec_rows with rec_length (single.go:411-423): start == stop one
+ * record, stop < start none, start or stop <= 0 or above rec_length InvalidIndexRange; sections of
+ * different level-1 records never merge.  SIZE: SizePart per part in wrapping int64 over file_size
+ * and chunk_size (any value ParseInt accepted, 0 and negatives included); host arithmetic.
+ * d_rows (nrows rows, idx_length = TotalUnits) is the index named in the request, d_rec_rows
+ * (rec_nrows, rec_length) the node's record index (CHUNK_RANGE only); both 16-byte aligned.
+ * Errors: SHOCKIDX_EFORMAT with Go's text (IndexNoFile / InvalidIndexRange / IndexOutBounds),
+ * *err_part (optional) = the failing part, else -1; result->count = result->size = 0 and d_secs is
+ * undefined.  Go's order of evaluation decides: part k's own parse or bounds error comes before any
+ * level-2 error of part k, and both after every error of a part before k.  d_rows == NULL is the
+ * missing index file at part 0 (modes 0-2); d_rec_rows == NULL is IndexNoFile at the first part whose
+ * level 1 yields a record, and no error when none does.  nparts == 0 succeeds with no sections.
+ * A short secs_cap returns SHOCKIDX_ESPACE with result->count = the sections needed, nothing
+ * written.  More than 2^20 parts, or more than INT32_MAX rows visited in one level, is
+ * SHOCKIDX_EINVAL. */
+int shockidx_download_plan(shockidx_ctx *ctx, int mode, const char *const *parts, uint64_t nparts,
+                           const void *d_rows, uint64_t nrows, int64_t idx_length,
+                           const void *d_rec_rows, uint64_t rec_nrows, int64_t rec_length,
+                           int64_t file_size, int64_t chunk_size,
+                           void *d_secs, uint64_t secs_cap, int64_t *err_part, shockidx_subset_result *result);
 
 /* ---- chunkrecord index -----------------------------------------
  * Indexers["chunkrecord"] (index/index.go:21-28, index/chunkrecord.go:41-99): rows of ~chunk

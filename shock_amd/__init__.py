@@ -15,5 +15,6 @@ See DESIGN.md and INTEGRATION.md.
 from ._lib import ShockIdxError, lib  # noqa: F401
 from .core import Context, IndexResult, MultiContext  # noqa: F401
 from .stream import Streamer  # noqa: F401
+from . import download  # noqa: F401,E402  (the ?download&index=..&part=.. branch, single.go:343-484)
 
-__all__ = ["Context", "IndexResult", "MultiContext", "ShockIdxError", "Streamer", "lib"]
+__all__ = ["Context", "IndexResult", "MultiContext", "ShockIdxError", "Streamer", "download", "lib"]

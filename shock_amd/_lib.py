@@ -20,6 +20,8 @@ FMT_NAMES = {FMT_NONE: None, FMT_FASTA: "fasta", FMT_FASTQ: "fastq", FMT_SAM: "s
 FMT_CODES = {"fasta": FMT_FASTA, "fastq": FMT_FASTQ, "sam": FMT_SAM, "line": FMT_LINE, None: FMT_AUTO,
              "auto": FMT_AUTO}
 
+PLAN_PART, PLAN_RANGE, PLAN_CHUNK_RANGE, PLAN_SIZE = 0, 1, 2, 3  # shockidx_plan_mode
+
 OK, EFORMAT, EINVAL, EHIP, ENOMEM, EIO, EINTERNAL, ESPACE = 0, 1, -1, -2, -3, -4, -5, -6
 
 EXPORTS = ("shockidx_ctx_create", "shockidx_ctx_destroy", "shockidx_build_device",
@@ -32,7 +34,7 @@ EXPORTS = ("shockidx_ctx_create", "shockidx_ctx_destroy", "shockidx_build_device
            "shockidx_subset_node",
            "shockidx_chunkrecord_device", "shockidx_chunkrecord_fd", "shockidx_chunkrecord_subset_device", "shockidx_create_subset_index",
            "shockidx_column_device", "shockidx_column_fd",
-           "shockidx_idx_part", "shockidx_idx_range", "shockidx_filter_device", "shockidx_stream_filter_device", "shockidx_ctx_trim",
+           "shockidx_idx_part", "shockidx_idx_range", "shockidx_filter_device", "shockidx_stream_filter_device", "shockidx_download_plan", "shockidx_ctx_trim",
            "shockidx_ctx_workspace_bytes", "shockidx_ctx_set_dev_cap", "shockidx_multi_create", "shockidx_multi_destroy", "shockidx_multi_rccl",
            "shockidx_multi_build_host", "shockidx_multi_build_fd", "shockidx_multi_create_index", "shockidx_multi_plan",
            "shockidx_multi_build_resident", "shockidx_device_count")
@@ -201,6 +203,10 @@ def lib():
     L.shockidx_stream_filter_device.argtypes = [vp, ctypes.c_char_p, vp, u64, vp, u64, vp, u64,
                                                 ctypes.POINTER(ctypes.c_int64), PSub]
     L.shockidx_stream_filter_device.restype = i32
+    L.shockidx_download_plan.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), u64, vp, u64, ctypes.c_int64,
+                                         vp, u64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp, u64,
+                                         ctypes.POINTER(ctypes.c_int64), PSub]
+    L.shockidx_download_plan.restype = i32
     L.shockidx_ctx_trim.argtypes = [vp, u64]
     L.shockidx_ctx_trim.restype = i32
     L.shockidx_ctx_workspace_bytes.argtypes = [vp]

@@ -451,6 +451,59 @@ class Context:
             d_out.free()
         return r
 
+    # -- the download plan (controller/node/single.go:372-483) ------------------------------------
+    def download_plan(self, mode: int, parts, d_rows, nrows: int, idx_length: int, d_rec_rows=None,
+                      rec_nrows: int = 0, rec_length: int = 0, file_size: int = 0, chunk_size: int = 0,
+                      d_secs=None, secs_cap: int = 0) -> SubsetResult:
+        """All parts of an index download as the Streamer's section list, left on the device
+        (shockidx_download_plan; mode: L.PLAN_*).  d_secs receives r.count records {int64 pos, int64
+        len}, r.size is Go's `size` (read as uint64); an error is EFORMAT with Go's text in r.err and
+        the failing part in r.err_part (-1: none); ESPACE: r.count = the sections needed."""
+        r = L.SubsetResult()
+        ep = ctypes.c_int64(-1)
+        arr = (ctypes.c_char_p * max(len(parts), 1))(*[p.encode() if isinstance(p, str) else bytes(p) for p in parts])
+        rc = self._lib.shockidx_download_plan(self._h, mode, arr, len(parts), d_rows, nrows, int(idx_length),
+                                              d_rec_rows, rec_nrows, int(rec_length), int(file_size),
+                                              int(chunk_size), d_secs, secs_cap, ctypes.byref(ep), ctypes.byref(r))
+        out = _sub_result(r, rc)
+        out.err_part = int(ep.value)
+        return out
+
+    def download_plan_host(self, mode: int, parts, rows, idx_length: int, rec_rows=None, rec_length: int = 0,
+                           file_size: int = 0, chunk_size: int = 0):
+        """Host-memory convenience: upload the index rows (None: the file is missing), plan on the
+        device, download.  Returns (secs int64[k, 2], size as Go's int64, err bytes|None, err_part)."""
+        bufs = []
+
+        def up(t):
+            if t is None:
+                return None, 0
+            t = np.ascontiguousarray(t).view(np.uint64).reshape(-1, 2)
+            b = self.alloc(16 * len(t) + 64)
+            bufs.append(b)
+            if len(t):
+                b.upload(t.tobytes())
+            return b.ptr, len(t)
+
+        try:
+            d_rows, nrows = up(rows)
+            d_rec, rec_nrows = up(rec_rows)
+            args = (mode, list(parts), d_rows, nrows, idx_length, d_rec, rec_nrows, rec_length, file_size, chunk_size)
+            r = self.download_plan(*args)  # sizes the output: ESPACE carries the sections needed
+            if r.status == L.ESPACE:
+                out = self.alloc(16 * r.count + 64)
+                bufs.append(out)
+                r = self.download_plan(*args, out.ptr, r.count)
+            if r.status == L.EFORMAT:
+                return np.zeros((0, 2), np.int64), 0, r.err, r.err_part
+            if r.status != L.OK:
+                raise RuntimeError(f"shockidx_download_plan: {r.status} {r.err!r}")
+            secs = out.rows(r.count).view(np.int64) if r.count else np.zeros((0, 2), np.int64)
+            return secs, _go_i64(r.size), None, -1
+        finally:
+            for b in bufs:
+                b.free()
+
     def detect(self, data):
         buf = np.frombuffer(bytes(data[:32768]), dtype=np.uint8)
         f = ctypes.c_int(0)
@@ -476,10 +529,17 @@ class SubsetResult:
     run_rows: np.ndarray | None = None
     gathered: bytes | None = None
     err_section: int = -1  # stream_filter_device: the failing section (Streamer.ESection)
+    err_part: int = -1  # download_plan: the failing part
 
     @property
     def ok(self) -> bool:
         return self.status == L.OK
+
+
+def _go_i64(x: int) -> int:
+    """a uint64 result word read as Go's int64"""
+    x &= (1 << 64) - 1
+    return x - (1 << 64) if x >> 63 else x
 
 
 def _sub_result(r: L.SubsetResult, rc: int) -> SubsetResult:

@@ -121,6 +121,7 @@ struct shockidx_ctx {
   u32 cr_grid = 0;                 //   k_cr_verify persistent grid
   Buf<uint8_t> d_cola{bufs};       // column index: the line table, then the cut offsets (bytes)
   Buf<uint8_t> d_colb{bufs};       //   flags, ranks, key spans, scan workspace (bytes)
+  Buf<uint8_t> d_plan{bufs};       // download plan: the level-2 workspace of CHUNK_RANGE (level 1 lives in d_sub)
   Buf<uint8_t> d_sec{bufs};        // sectioned stream: one large section staged 16-byte aligned, and its output (bytes)
   hipStream_t s_copy = nullptr;    // slab-pipelined host builds: the H2D stream
   uint8_t *h_rows[2] = {nullptr, nullptr};  // slab-pipelined fd builds: pinned row staging (D2H)

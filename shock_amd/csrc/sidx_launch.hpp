@@ -121,5 +121,17 @@ hipError_t sidx_range_emit(const sidx::u64 *rows, sidx::u64 nrows, sidx::u64 a0,
 hipError_t sidx_gather(const uint8_t *data, sidx::u64 data_len, const sidx::u64 *runs, sidx::u64 bound,
     sidx::u64 *ctl, sidx::u64 *lens, sidx::u64 *outoff, void *tmp, size_t *tmp_bytes, sidx::u64 *wfirst,
     uint8_t *out, sidx::u64 out_cap, hipEvent_t e0, hipEvent_t e1, hipStream_t s);
+// the download plan (sidx_plan.hip; control words: sidx_plan.hpp): one level over V > 0 row visits of
+// nseg segments (section count into ctl[word], the sections into out when they fit cap); the level-2
+// segments of CHUNK_RANGE from the level-1 records; Idx.Part per part
+hipError_t sidx_plan_init(sidx::u64 *ctl, hipStream_t s);
+hipError_t sidx_plan_level(const sidx::u64 *rows, sidx::u64 nrows, const sidx::u64 *a0, const sidx::u64 *off,
+    sidx::u64 nseg, sidx::u64 V, sidx::u32 *flags, sidx::u32 *vseg, sidx::u64 *id, void *tmp, size_t *tmp_bytes,
+    sidx::u64 *ctl, int word, sidx::u64 cap, sidx::u64 *out, sidx::u32 *part, const sidx::u32 *segpart,
+    sidx::u64 *size, hipStream_t s);
+hipError_t sidx_plan_segments(const sidx::u64 *recs, const sidx::u32 *part, sidx::u64 bound, sidx::u64 *ctl,
+    sidx::i64 rec_length, sidx::u64 *a0, sidx::u64 *nr, sidx::u64 *off, void *tmp, size_t *tmp_bytes, hipStream_t s);
+hipError_t sidx_plan_part(const sidx::u64 *rows, sidx::u64 nrows, const sidx::u64 *a0, const sidx::u64 *b0,
+    sidx::u64 P, sidx::u64 *out, sidx::u64 *size, hipStream_t s);
 
 }  // extern "C"

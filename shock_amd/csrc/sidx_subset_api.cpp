@@ -12,9 +12,11 @@
 #include "sidx_subset.hpp"
 #include "sidx_launch.hpp"
 #include "sidx_host.hpp"
+#include "sidx_plan_host.hpp"
 
 using namespace sidx;
 using namespace sidx_host;
+using namespace sidx_plan;  // the part strings and Go's error texts
 
 // ---- Subset nodes ------------------------------------------------------------------------
 namespace {
@@ -327,58 +329,6 @@ int shockidx_create_subset_index(shockidx_ctx *c, const void *d_ids, uint64_t id
 
 // ---- Index read path: Idx.Part / Idx.Range (index/index.go:67-193) ------------------------
 namespace {
-
-const char E_IDX_RANGE[] = "Invalid index record range";  // errors/errors.go:21-23
-const char E_IDX_BOUNDS[] = "Index record out of bounds";
-const char E_IDX_NOFILE[] = "Index file is missing";
-
-// strconv.ParseInt(s, 10, 64); any error (syntax or range) is reported the same by the callers
-bool go_parse_int64(const char *s, size_t n, i64 *v) {
-  size_t i = 0;
-  bool neg = false;
-  if (n == 0) return false;
-  if (s[0] == '+' || s[0] == '-') {
-    neg = s[0] == '-';
-    i = 1;
-  }
-  if (i == n) return false;
-  u64 u = 0;
-  for (; i < n; ++i) {
-    const unsigned d = (unsigned char)s[i] - '0';
-    if (d > 9 || u > (~0ull - d) / 10) return false;
-    u = u * 10 + d;
-  }
-  if (!neg && u > (u64)INT64_MAX) return false;
-  if (neg && u > (u64)INT64_MAX + 1) return false;
-  *v = neg ? (i64)(0 - u) : (i64)u;
-  return true;
-}
-
-// the part string: 0 = one record, 1 = a range start-end (strings.Split(part, "-")[0], [1]),
-// -1 = Go's error text in *e
-int parse_part(const char *part, i64 idx_length, i64 *a, i64 *b, const char **e) {
-  const char *dash = strchr(part, '-');
-  if (dash) {  // index.go:77-84 / :129-136
-    const char *s1 = dash + 1, *d2 = strchr(s1, '-');
-    i64 start = 0, end = 0;
-    const bool ok0 = go_parse_int64(part, (size_t)(dash - part), &start);
-    const bool ok1 = go_parse_int64(s1, d2 ? (size_t)(d2 - s1) : strlen(s1), &end);
-    if (!ok0 || !ok1 || start <= 0 || start > idx_length || end <= 0 || end > idx_length) {
-      *e = E_IDX_RANGE;
-      return -1;
-    }
-    *a = start;
-    *b = end;
-    return 1;
-  }
-  i64 p = 0;  // index.go:100-105 / :178-183
-  if (!go_parse_int64(part, strlen(part), &p) || p <= 0 || p > idx_length) {
-    *e = E_IDX_BOUNDS;
-    return -1;
-  }
-  *a = *b = p;
-  return 0;
-}
 
 // row i of the device table (16 bytes D2H); a row past the table reads as `dflt`
 int read_row(shockidx_ctx *c, const void *d_rows, u64 nrows, u64 i, const u64 dflt[2], u64 out[2],
