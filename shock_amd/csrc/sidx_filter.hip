@@ -815,6 +815,7 @@ extern "C" hipError_t sidx_filter_write(const uint8_t *data, u64 n, const u64 *r
   return hipGetLastError();
 }
 extern "C" u64 sidx_filter_block() { return FW_BLOCK; }
+extern "C" u32 sidx_filter_recs() { return FW_RECS; }  // records staged per output block
 
 extern "C" u32 sidx_fa_slot() { return FSLOT; }
 // FASTA boundaries (anonymize): lnl / lgt / cnl / cgt / tcnt / toff: ntile = ceil(n / TILE)

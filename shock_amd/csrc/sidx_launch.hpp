@@ -68,6 +68,10 @@ hipError_t sidx_scan_flags(const sidx::u32 *in, sidx::u64 *out, sidx::u64 n, voi
     hipStream_t s);
 hipError_t sidx_scan_u64(const sidx::u64 *in, sidx::u64 *out, sidx::u64 n, void *tmp, size_t *tmp_bytes,
     hipStream_t s);
+hipError_t sidx_scan_max_u64(const sidx::u64 *in, sidx::u64 *out, sidx::u64 n, void *tmp, size_t *tmp_bytes,
+    hipStream_t s);
+sidx::u64 sidx_scan_block();
+sidx::u64 sidx_scan_small_items();
 // column index (sidx_column.hip): the scans' temp bytes for L lines; the build up to the cut
 // offsets (written over the line table lt); the rows from them; the SHOCKIDX_VERIFY end check
 sidx::u64 sidx_col_scan_bytes(sidx::u64 L);
@@ -102,6 +106,7 @@ hipError_t sidx_filter_write(const uint8_t *data, sidx::u64 n, const sidx::u64 *
     const sidx::u64 *outlen, const sidx::u64 *outoff, sidx::u64 K, sidx::u64 total, int kind, sidx::u64 *wfirst,
     uint8_t *out, const sidx::u32 *ord, hipStream_t s);
 sidx::u64 sidx_filter_block();
+sidx::u32 sidx_filter_recs();
 hipError_t sidx_filter_read_status(const uint8_t *data, sidx::u64 n, sidx::u64 start, sidx::u32 *out,
     hipStream_t s);
 // the sectioned stream (sidx_stream.hip; control words: sidx_stream.hpp): range check and the sections

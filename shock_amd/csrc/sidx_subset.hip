@@ -551,6 +551,13 @@ extern "C" hipError_t sidx_scan_flags(const u32 *in, u64 *out, u64 n, void *tmp,
 extern "C" hipError_t sidx_scan_u64(const u64 *in, u64 *out, u64 n, void *tmp, size_t *tmp_bytes, hipStream_t s) {
   return dscan::run<u64, dscan::Sum, true>(tmp, tmp_bytes, in, out, n, s);
 }
+// exclusive running maximum over u64 (the identity is 0): the column index's and the FASTA boundaries' carry
+extern "C" hipError_t sidx_scan_max_u64(const u64 *in, u64 *out, u64 n, void *tmp, size_t *tmp_bytes, hipStream_t s) {
+  return dscan::run<u64, dscan::Max, true>(tmp, tmp_bytes, in, out, n, s);
+}
+// the scans' shape (tests take their sizes from these): items per workgroup; the largest input of the three-launch path
+extern "C" u64 sidx_scan_block() { return dscan::BLOCK; }
+extern "C" u64 sidx_scan_small_items() { return dscan::SMALL_BLOCKS * dscan::BLOCK; }
 
 extern "C" hipError_t sidx_subset_compact(const u32 *keep, const u64 *rank, const i64 *val, const u32 *st, u64 m,
                                           i64 *cval, u32 *cst, u64 *cline, u64 *ctl, hipStream_t s) {
