@@ -258,6 +258,16 @@ class Context:
         if rc != L.OK:
             raise L.ShockIdxError(rc, "shockidx_ctx_trim failed")
 
+    def debug_set_tiles_grid(self, g: int) -> None:
+        """Debug entry (shockidx_debug_set_tiles_grid, not in the public header): run every tile pass on
+        at most g workgroups, so a test reaches the edges of the claim plan with a few MiB.  Only before
+        the context's first build."""
+        fn = self._lib.shockidx_debug_set_tiles_grid  # (bound here: a variant library of older sources has none)
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_int], ctypes.c_int
+        rc = fn(self._h, int(g))
+        if rc != L.OK:
+            raise L.ShockIdxError(rc, "shockidx_debug_set_tiles_grid failed (after the first build, or g out of range)")
+
     def workspace_bytes(self) -> int:
         return int(self._lib.shockidx_ctx_workspace_bytes(self._h))
 

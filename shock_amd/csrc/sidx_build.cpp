@@ -278,6 +278,7 @@ int run_index(shockidx_ctx *c, const uint8_t *d_data, u64 n, int kfmt, u64 *d_ro
   p.pgrid = c->tiles_grid < ntiles ? c->tiles_grid : (u32)ntiles;
   p.fix = general ? nullptr : c->d_fix.get();  // null: the two-pass build (k_index1) for every format
   p.fixcap = (u32)c->tiles_cap();
+  p.grid_cap = c->grid_cap;
   p.badkey = (u64 *)(c->d_small + SMALL_BADKEY + 8 * slot);
   p.badkey_next = (u64 *)(c->d_small + SMALL_BADKEY + 8 * (slot ^ 1));
   p.detail = c->d_detail;

@@ -434,6 +434,15 @@ int shockidx_debug_timing(shockidx_ctx *c, uint64_t *out, uint32_t nwg) {
 
 int shockidx_debug_tiles_grid(shockidx_ctx *c) { return c ? (int)c->tiles_grid : 0; }
 
+// Diagnostic (not in the public header): run every tile pass of this context on at most g
+// workgroups, so a test reaches every edge of the claim plan (sidx_claim.hpp) with a few MiB.
+// Only before the context's first build (the workspace is sized by the grid); g in 1..the grid.
+int shockidx_debug_set_tiles_grid(shockidx_ctx *c, int g) {
+  if (!c || c->epoch != 0 || g < 1 || (u32)g > c->tiles_grid) return SHOCKIDX_EINVAL;
+  c->tiles_grid = c->grid_cap = (u32)g;
+  return SHOCKIDX_OK;
+}
+
 // Diagnostic (not in the public header): test hooks of the context (shockidx_ctx::inject);
 // returns the previous flags.  The next build that grows the status arrays takes bits 0-1.
 int shockidx_debug_inject(shockidx_ctx *c, uint32_t flags) {

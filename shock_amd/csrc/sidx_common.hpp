@@ -96,7 +96,7 @@ struct SlabParams {
   u64 *badkey;           // min first-bad key (KEY_NONE before launch)
   u64 *detail;           // per-tile {pos, len} of the tile's first bad record (FASTA msg)
   u32 *counters;         // [0] unused, [1] defer overflow, [2] k_fixup items, [3] k_fixup overflow,
-                         // [4] [5] scan tickets, [6] unused, [7] k_fixup finish ticket (NCOUNTERS, reset by the previous finalize)
+                         // [4] [5] scan tickets, [6] the tile pass's claim tickets (claim_loop), [7] k_fixup finish ticket (NCOUNTERS, reset by the previous finalize)
   u64 *badkey_next;      // the other build's first-bad slot (reset by finalize)
   u32 *counters_next;    // the other build's counters (reset by finalize)
   u32 ntiles;
@@ -118,6 +118,7 @@ struct SlabParams {
   u32 seq;               // multi-GPU: the caller's build tag, stamped into the slab summary
   u64 *fix;              // k_fixup queue (FixRec items, 24 bytes); counters[2] = items, counters[3] = overflow
   u32 fixcap;
+  u32 grid_cap;          // test hook (shockidx_debug_set_tiles_grid): no tile pass runs on a larger grid; 0: none
   // exclusive monoid prefix of every tile's aggregate (k_scan_excl): k_index1's incoming
   // states, the tile passes' record / row bases
   const u64 *tile_excl;

@@ -103,6 +103,7 @@ struct shockidx_ctx {
   int spec_fmt = 0;            // the last detected format (speculated by the next AUTO build)
   u64 *d_timing = nullptr;     // diagnostic phase timing buffer (SHOCKIDX_TIMING)
   u32 tiles_grid = 0;               // persistent grid of the tile passes (CUs x co-resident)
+  u32 grid_cap = 0;                 // test hook (shockidx_debug_set_tiles_grid): the largest grid of any tile pass, 0: none
   uint8_t *h_stage[sidx_host::NSTAGE] = {nullptr, nullptr};
   sidx::DevResult *h_res = nullptr;
   sidx_host::CopyPool *pool = nullptr;  // host memcpy threads for the host-memory entry points

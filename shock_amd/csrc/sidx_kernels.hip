@@ -21,6 +21,7 @@
 #include <hip/hip_ext.h>
 #include <atomic>
 
+#include "sidx_claim.hpp"
 #include "sidx_common.hpp"
 #include "sidx_device.hpp"
 #include "sidx_launch.hpp"
@@ -914,6 +915,54 @@ __device__ __forceinline__ void g_min64(u64 *p, u64 v) {
                                __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The claim loop of a persistent tile pass (k_fq_tiles, k_fa_tiles; the plan: sidx_claim.hpp).
+// A workgroup's first claim is its block index; every later one is G + a ticket of counters[6]
+// (zero at a build's start like the other counters: the previous build's finalize, or the host's
+// reset of a dirty slot).  Tickets rise, so claims start in file order, and claims G.. go to
+// whichever workgroup asks first.  body(t, r) runs one tile of the claim r = [tb, te) and holds
+// at least one workgroup barrier.
+//
+// The ticket's latency (1-3 us under the streaming load, against ~5 us per tile) is hidden:
+// thread 0 issues the atomic CLAIM_AHEAD tiles before the claim's end (at its first tile when it
+// is shorter), right before that tile's DMA, so the wait the tile makes for its DMA anyway --
+// the explicit s_waitcnt vmcnt(0) in the body -- covers the ticket too.  The DMA is inline asm the
+// compiler does not count, so to the compiler the ticket is the only load in flight and it puts a
+// vmcnt(0) of its own before the first read of `nx`: that read is therefore placed before the
+// *next* tile's DMA issue, after the explicit wait of the tile the ticket travelled with, where
+// nothing is left to wait for.  There thread 0 writes the ticket to one word of the workgroup's
+// LDS block (`word`); the barriers of that tile and the later ones publish it, and every wave
+// reads it after the claim's last tile.  The word is written again only after a barrier of the
+// next claim, which no wave reaches before it has read the word.  No barrier is added.
+// Every claim but the plan's last has two tiles or more (claim_plan), which this needs; after
+// the last claim every ticket is past the end, so its workgroup asks for none.
+constexpr u32 CLAIM_AHEAD = 8;  // tiles before a claim's end at which its workgroup asks for the next
+template <class Body>
+__device__ __forceinline__ void claim_loop(const SlabParams &p, u32 &word, int tid, Body &&body) {
+  const ClaimPlan cp = claim_plan(p.ntiles, p.pgrid);
+  u32 nx = 0;  // thread 0: the next claim's ticket
+  for (u32 c = blockIdx.x; c < cp.nclaims;) {
+    const ClaimRange r = claim_range(cp, c);
+    const bool more = c + 1 < cp.nclaims;
+    const u32 ta = r.te - r.tb > CLAIM_AHEAD ? r.te - CLAIM_AHEAD : r.tb;
+    for (u32 t = r.tb; t < r.te; ++t) {
+      if (more && tid == 0) {
+        if (t == ta) {
+          // (an offset the compiler cannot see through: on an address it knows to be uniform it
+          // would fold the lanes' adds into one and read the result back with a readfirstlane --
+          // and a wait for the ticket -- right here, ahead of the DMA)
+          u32 z = 0;
+          asm("" : "+v"(z));
+          nx = g_add(&p.counters[6] + z, 1u);
+        }
+        if (t == ta + 1) word = nx;
+      }
+      body(t, r);
+    }
+    if (!more) break;
+    c = p.pgrid + (u32)__builtin_amdgcn_readfirstlane((int)word);
+  }
+}
+
 __device__ __forceinline__ void push_fix(const SlabParams &p, u64 start, u64 g, u32 tile) {
   const u32 i = g_add(&p.counters[2], 1u);
   if (i < p.fixcap) {
@@ -971,11 +1020,13 @@ __device__ __forceinline__ u32 *fq_defer(const SlabParams &p, u64 t) { return p.
 // A workgroup keeps the lines and tile words of FQ_BLK consecutive tiles in LDS, so they leave as
 // one 2 KiB burst of lines and one 128-byte line of words per FQ_BLK tiles (profiles/r06/calls/e:
 // the kernel 1.872 -> 1.855 ms and the build 1.998 -> 1.982 on each of four input copies, against
-// one tile per burst).  The tiles come in batches of FQ_RR consecutive tiles dealt round-robin to
-// the workgroups (k_fq_tiles).
+// one tile per burst).  The tiles come in claims of up to CLAIM_BMAX consecutive tiles that the
+// workgroups take in file order (k_fq_tiles, sidx_claim.hpp); a claim's bursts start at its first
+// tile, and one shorter than FQ_BLK tiles leaves at the claim's end.
 constexpr u32 FQ_BLK = 16;
-constexpr u64 FQ_RR = 32;
-static_assert(FQ_RR % FQ_BLK == 0, "a batch holds whole bursts");
+static_assert(CLAIM_BMIN % 2 == 0 && FQ_BLK % 2 == 0,
+              "claims, and so bursts, start at even tiles: the tile words leave 16 bytes per lane");
+static_assert(CLAIM_BMAX <= 32, "a claim holds at most 32 tiles (the batch size measured best)");
 struct __align__(16) TilesSmem {
   uint16_t nlpos[SNLCAP + 8];        // + 8: the certifier reads aligned 8-entry windows
   uint16_t line[FQ_BLK][FQ_LINE_E];  // the batch's lines: a tile's first FQ_LINE_E entries each
@@ -1257,26 +1308,24 @@ __global__ __launch_bounds__(SNT, SIDX_TILES_WGS) void k_fq_tiles(const SlabPara
   if (gated_off(p)) return;  // format speculation failed: the host re-runs with the detected format
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const u64 G = p.pgrid;
   u64 tacc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   u64 *tacc = (tmg(p) && (tid == 0 || tid == 64)) ? tacc_ : nullptr;
   u64 ntl = 0;
-  // batches of FQ_RR consecutive tiles dealt round-robin to the workgroups (a tile's halo, the
-  // first KiB of the next tile, is read again by the same workgroup through its own L2 except at a
-  // batch's end).  Where the workgroups' concurrent streams sit in the input decides how fast
-  // they run together: in one process over the C2 input (profiles/r06/calls/j/ab_fq_rr*.json, every
-  // table hashed and equal) batches of 32 ran 1.834-2.034 ms where a contiguous block of 368
+  // Claims of up to 32 consecutive tiles taken in file order (a tile's halo, the first KiB of the
+  // next tile, is read again by the same workgroup through its own L2 except at a claim's end).
+  // Where the workgroups' concurrent streams sit in the input decides how fast they run together:
+  // in one process over the C2 input (profiles/r06/calls/j/ab_fq_rr*.json, every table hashed and
+  // equal) batches of 32 dealt round-robin ran 1.834-2.034 ms where a contiguous block of 368
   // tiles per workgroup (round 6 before) ran 1.987-2.118, faster on each of eight input copies
-  // over three boxes; batches of 8, 16, 24, 48 or 64, or a last round split evenly, all ran slower than 32
-  const u64 nbat = (p.ntiles + FQ_RR - 1) / FQ_RR;
-  for (u64 c = blockIdx.x; c < nbat; c += G) {
-    const u64 tb = c * FQ_RR, te = tb + FQ_RR < p.ntiles ? tb + FQ_RR : p.ntiles;
-    for (u64 t = tb; t < te; ++t) {
-      const u32 j = (u32)(t - tb) & (FQ_BLK - 1);  // (bursts start at even tiles: the words leave 16 bytes per lane)
-      tiles_iter<kSpans>(p, S, raw, t, tid, lane, wid, tacc, j, j == FQ_BLK - 1 || t + 1 == te);
-      ++ntl;
-    }
-  }
+  // over three boxes; batches of 8, 16, 24, 48 or 64, or a last round split evenly, all ran slower
+  // than 32.  The claims keep that order and hand it out by a counter (claim_loop): no workgroup
+  // is left with a twelfth batch while others have finished their eleventh, and one that falls
+  // behind takes fewer (DESIGN.md §3 "Tile order").
+  claim_loop(p, S.pad, tid, [&](u32 t, const ClaimRange &r) {
+    const u32 j = (t - r.tb) & (FQ_BLK - 1);  // (bursts start at even tiles: the words leave 16 bytes per lane)
+    tiles_iter<kSpans>(p, S, raw, t, tid, lane, wid, tacc, j, j == FQ_BLK - 1 || t + 1 == r.te);
+    ++ntl;
+  });
   if (tacc) {  // per workgroup: wave 0's phases in slots 0-5, wave 1's in the next 9-slot record
     u64 *o = tmg(p) + ((u64)blockIdx.x * 2 + (tid ? 1 : 0)) * 9;
     for (int i = 0; i < 8; ++i) o[i] = tacc[i];
@@ -2244,10 +2293,10 @@ __device__ __forceinline__ void fa_iter(const SlabParams &p, FaSmem &S, uint8_t 
   }
 }
 
-// one LDS slot, batches of FA_RR consecutive tiles dealt round-robin to the workgroups (as
-// k_fq_tiles): in one process over three copies of the C3 input (profiles/r06/calls/j/ab_fa_rr32.json)
-// 1.858-1.994 ms against 1.896-2.020 for single tiles in XCD-major grid-stride order (round 5)
-constexpr u64 FA_RR = 32;
+// one LDS slot, claims of up to 32 consecutive tiles taken in file order (as k_fq_tiles): in one
+// process over three copies of the C3 input (profiles/r06/calls/j/ab_fa_rr32.json) batches of 32
+// dealt round-robin ran 1.858-1.994 ms against 1.896-2.020 for single tiles in XCD-major
+// grid-stride order (round 5)
 #ifndef SIDX_FA_WGS
 #define SIDX_FA_WGS 7  // 19.1 KiB of LDS (no halo in the slot); 8 per CU (<= 64 VGPRs) measured the same
 #endif
@@ -2257,12 +2306,7 @@ __global__ __launch_bounds__(SNT, SIDX_FA_WGS) void k_fa_tiles(const SlabParams 
   if (gated_off(p)) return;  // format speculation failed: the host re-runs with the detected format
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const u64 G = p.pgrid;
-  const u64 nbat = (p.ntiles + FA_RR - 1) / FA_RR;
-  for (u64 c = blockIdx.x; c < nbat; c += G) {
-    const u64 tb = c * FA_RR, te = tb + FA_RR < p.ntiles ? tb + FA_RR : p.ntiles;
-    for (u64 t = tb; t < te; ++t) fa_iter(p, S, raw, t, tid, lane, wid);
-  }
+  claim_loop(p, S.pad[0], tid, [&](u32 t, const ClaimRange &) { fa_iter(p, S, raw, t, tid, lane, wid); });
 }
 
 // first boundary of tile u given its words and entering state: the conditional '>' when the
@@ -2908,6 +2952,7 @@ extern "C" hipError_t sidx_launch_tiles(TilePass pass, const SlabParams *pp, Dev
                                         hipEvent_t ek0, hipEvent_t ek1) {
   SlabParams p = *pp;
   if (pass == TP_FA || pass == TP_LINE || pass == TP_SAM) p.pgrid = tile_grid(p, pass);
+  if (p.grid_cap && p.pgrid > p.grid_cap) p.pgrid = p.grid_cap;
   switch (pass) {
     case TP_FQ: return launch_fq(p, d_res, s, ek0, ek1);
     case TP_FA: return launch_fa(p, d_res, s, ek0, ek1);
