@@ -226,6 +226,7 @@ __device__ __forceinline__ u32 wave_scan_add(u32 v) {
 }
 
 __device__ __forceinline__ u32 umax(u32 a, u32 b) { return a > b ? a : b; }
+__device__ __forceinline__ u32 umin(u32 a, u32 b) { return a < b ? a : b; }
 
 // lanes below this one with their bit set in b
 __device__ __forceinline__ u32 mbcnt64(u64 b) {

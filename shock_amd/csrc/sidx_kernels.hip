@@ -889,13 +889,14 @@ __device__ __forceinline__ bool fq_ok(const uint8_t *r, u32 s, u32 e0, u32 e1, u
 
 // FASTQ phase read off the tile: the first newline c (of the first 16) after which an
 // '@' line, a sequence line, a '+' line and an equal-length quality line follow.
-__device__ __forceinline__ u32 fq_guess_at(const uint8_t *raw, const uint16_t *nlpos, u32 TT, int lane) {
+// (plane: the lane number for the predicate, TilePred)
+__device__ __forceinline__ u32 fq_guess_at(const uint8_t *raw, const uint16_t *nlpos, u32 TT, int lane, int plane) {
   // branch-free: every lane reads (clamped indices, values ignored where not valid), so the
   // two LDS rounds are not serialised behind branches
   const u32 c = (u32)lane & 15u;
   const u32 a = nlpos[c], b1 = nlpos[c + 1], b2 = nlpos[c + 2], b3 = nlpos[c + 3], b4 = nlpos[c + 4];
   const u32 x = raw[FRONT + a + 1], y = raw[FRONT + b2 + 1];
-  const bool ok = ((u32)lane < 16) & (c + 4 < TT) & (x == '@') & (y == '+') & (b2 - b1 > 1) & ((b2 - b1) == (b4 - b3));
+  const bool ok = ((u32)plane < 16) & (c + 4 < TT) & (x == '@') & (y == '+') & (b2 - b1 > 1) & ((b2 - b1) == (b4 - b3));
   const u64 m = __ballot(ok);
   return m ? (ctz64(m) & 3u) : GUESS_NONE;
 }
@@ -935,31 +936,79 @@ __device__ __forceinline__ void g_min64(u64 *p, u64 v) {
 // next claim, which no wave reaches before it has read the word.  No barrier is added.
 // Every claim but the plan's last has two tiles or more (claim_plan), which this needs; after
 // the last claim every ticket is past the end, so its workgroup asks for none.
+//
+// Registers.  The tile loop keeps no SlabParams field live: left to itself the compiler hoists every
+// field, every 64-bit bound and every thread predicate the body touches out of the loop, runs out of
+// scalar registers and reloads them from spill lanes between every pair of barriers.  So
+//   * the kernel's parameters are read where they are used through kargs(), the kernel argument
+//     block behind a pointer the compiler cannot see through (scalar loads that hit the constant
+//     cache): once per claim for the plan and the claim's bytes, and in the cold branches of a tile;
+//   * a tile's bounds are 32-bit offsets from its claim's first byte (ClaimBytes: a claim holds at
+//     most CLAIM_BMAX tiles);
+//   * the thread predicates of a tile (tid == 0, lane == 63, wid == 3 ...) are taken from copies of
+//     tid / lane / wid made opaque once per tile (TilePred): one compare where each is used.
 constexpr u32 CLAIM_AHEAD = 8;  // tiles before a claim's end at which its workgroup asks for the next
+typedef const __attribute__((address_space(4))) SlabParams *KArgs;
+// the kernel's SlabParams (its only parameter, at offset 0 of the argument block)
+__device__ __forceinline__ KArgs kargs() {
+  KArgs k = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return k;
+}
+struct TilePred {
+  int tid, lane, wid;
+};
+__device__ __forceinline__ TilePred tile_pred(int tid, int lane, int wid) {
+  TilePred q = {tid, lane, wid};
+  asm volatile("" : "+v"(q.tid), "+v"(q.lane), "+s"(q.wid));
+  return q;
+}
+constexpr u32 CLAIM_SAT = (CLAIM_BMAX + 2) * (u32)TILE;  // past any offset a claim's tiles reach
+struct ClaimBytes {
+  const uint8_t *base;  // the claim's first byte: data + tb * TILE
+  u32 nrel, erel;       // the slab's owned (n) and readable (end) bytes from base on, at most CLAIM_SAT
+  // tile `rel` of the claim: the bytes it owns and the bytes readable from its first byte on
+  __device__ __forceinline__ u32 tlen(u32 rel) const { return umin(nrel - rel * TILE, (u32)TILE); }
+  __device__ __forceinline__ u32 llen(u32 rel) const { return umin(erel - rel * TILE, (u32)(TILE + SHALO)); }
+};
+// tile t has fewer than FRONT readable bytes in front of it (the slab's first tile only)
+__device__ __forceinline__ bool tile_nofront(u32 t) { return t == 0 && kargs()->front < FRONT; }
 template <class Body>
-__device__ __forceinline__ void claim_loop(const SlabParams &p, u32 &word, int tid, Body &&body) {
-  const ClaimPlan cp = claim_plan(p.ntiles, p.pgrid);
+__device__ __forceinline__ void claim_loop(u32 &word, int tid, Body &&body) {
   u32 nx = 0;  // thread 0: the next claim's ticket
-  for (u32 c = blockIdx.x; c < cp.nclaims;) {
+  for (u32 c = blockIdx.x;;) {
+    const KArgs k = kargs();
+    const ClaimPlan cp = claim_plan(k->ntiles, k->pgrid);
+    if (c >= cp.nclaims) break;
     const ClaimRange r = claim_range(cp, c);
-    const bool more = c + 1 < cp.nclaims;
+    const u32 more = (u32)__builtin_amdgcn_readfirstlane((int)(c + 1 < cp.nclaims));  // (one scalar, no lane mask)
     const u32 ta = r.te - r.tb > CLAIM_AHEAD ? r.te - CLAIM_AHEAD : r.tb;
+    const u64 lo = (u64)r.tb * TILE, nleft = k->n - lo, eleft = k->end - lo;
+    ClaimBytes cb;
+    cb.base = k->data + lo;
+    cb.nrel = nleft < CLAIM_SAT ? (u32)nleft : CLAIM_SAT;
+    cb.erel = eleft < CLAIM_SAT ? (u32)eleft : CLAIM_SAT;
     for (u32 t = r.tb; t < r.te; ++t) {
-      if (more && tid == 0) {
-        if (t == ta) {
-          // (an offset the compiler cannot see through: on an address it knows to be uniform it
-          // would fold the lanes' adds into one and read the result back with a readfirstlane --
-          // and a wait for the ticket -- right here, ahead of the DMA)
-          u32 z = 0;
-          asm("" : "+v"(z));
-          nx = g_add(&p.counters[6] + z, 1u);
+      if (more && t - ta <= 1u) {  // t == ta or ta + 1 (uniform: the predicate below is not kept over the loop)
+        int t0 = tid;
+        asm volatile("" : "+v"(t0));
+        if (t0 == 0) {
+          if (t == ta) {
+            // (an offset the compiler cannot see through: on an address it knows to be uniform it
+            // would fold the lanes' adds into one and read the result back with a readfirstlane --
+            // and a wait for the ticket -- right here, ahead of the DMA)
+            u32 z = 0;
+            asm("" : "+v"(z));
+            nx = g_add(&kargs()->counters[6] + z, 1u);
+          } else {
+            word = nx;
+          }
         }
-        if (t == ta + 1) word = nx;
       }
-      body(t, r);
+      body(t, r, cb);
     }
     if (!more) break;
-    c = p.pgrid + (u32)__builtin_amdgcn_readfirstlane((int)word);
+    c = kargs()->pgrid + (u32)__builtin_amdgcn_readfirstlane((int)word);
   }
 }
 
@@ -1023,7 +1072,10 @@ __device__ __forceinline__ u32 *fq_defer(const SlabParams &p, u64 t) { return p.
 // one tile per burst).  The tiles come in claims of up to CLAIM_BMAX consecutive tiles that the
 // workgroups take in file order (k_fq_tiles, sidx_claim.hpp); a claim's bursts start at its first
 // tile, and one shorter than FQ_BLK tiles leaves at the claim's end.
-constexpr u32 FQ_BLK = 16;
+#ifndef SIDX_FQ_BLK
+#define SIDX_FQ_BLK 16
+#endif
+constexpr u32 FQ_BLK = SIDX_FQ_BLK;
 static_assert(CLAIM_BMIN % 2 == 0 && FQ_BLK % 2 == 0,
               "claims, and so bursts, start at even tiles: the tile words leave 16 bytes per lane");
 static_assert(CLAIM_BMAX <= 32, "a claim holds at most 32 tiles (the batch size measured best)");
@@ -1035,18 +1087,38 @@ struct __align__(16) TilesSmem {
   u32 nh, ndefer, slow, pad;
 };
 
-// entry L of the tile being certified (batch slot j): its line in LDS, or the overflow slot
-__device__ __forceinline__ void fq_put(const SlabParams &p, TilesSmem &S, u64 t, u32 j, u32 L, uint16_t v) {
-  if (L < FQ_LINE_E) S.line[j][L] = v;
-  else __builtin_nontemporal_store(v, reinterpret_cast<uint16_t *>(p.tile_stage) + fq_ovf(p, t) + (L - FQ_LINE_E));
+// entry L of the tile being certified (batch slot j): its line in LDS, or the overflow slot (a tile
+// of more than 63 records: the slot's address is read off the kernel arguments there)
+__device__ __forceinline__ void fq_put(TilesSmem &S, u32 t, u32 j, u32 L, uint16_t v) {
+  if (L < FQ_LINE_E) {
+    S.line[j][L] = v;
+  } else {
+    const KArgs k = kargs();
+    uint16_t *ovf = reinterpret_cast<uint16_t *>(k->tile_stage) + ((u64)k->ntiles * FQ_LINE_E + (u64)t * FQ_OVF);
+    __builtin_nontemporal_store(v, ovf + (L - FQ_LINE_E));
+  }
+}
+// the buffer descriptor of tile_rsrc from a tile's first byte and its readable length
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc_at(const uint8_t *tile0, u32 llen) {
+  const u64 ba = (u64)tile0;
+  const uint8_t *sbase = (const uint8_t *)(((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)ba)) |
+                                           ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(ba >> 32)) << 32));
+  return __builtin_amdgcn_make_buffer_rsrc((void *)sbase, (short)0, (int)__builtin_amdgcn_readfirstlane((int)llen),
+                                           0x00020000);
 }
 
 template <bool kSpans>
-__device__ __forceinline__ void tiles_iter(const SlabParams &p, TilesSmem &S, uint8_t *raw, u64 t, int tid, int lane,
-                                           int wid, u64 *tacc, u32 j, bool flush) {
+__device__ __forceinline__ void tiles_iter(const SlabParams &p, const ClaimBytes &cb, u32 rel, TilesSmem &S,
+                                           uint8_t *raw, u32 t, int tid, int lane, int wid, u64 *tacc, u32 j,
+                                           bool flush) {
   // diagnostic phase stamps (SIDX_DIAG builds with SHOCKIDX_TIMING; tacc == nullptr otherwise):
   // lane 0 of waves 0 (the certifying wave) and 1 accumulate the cycles of each phase
   u64 tprev = tacc ? stamp() : 0;
+  const TilePred q_ = tile_pred(tid, lane, wid);  // (predicates only: addresses use tid / lane / wid)
+  const int ptid = q_.tid, plane = q_.lane, pwid = q_.wid;
+  const u32 tlen = cb.tlen(rel), llen = cb.llen(rel);
+  const uint8_t *tile0 = cb.base + rel * (u32)TILE;
+  const bool nofront = tile_nofront(t);
 #define TILES_STAMP(i)              \
   if (tacc) {                       \
     const u64 tn_ = stamp();        \
@@ -1059,18 +1131,14 @@ __device__ __forceinline__ void tiles_iter(const SlabParams &p, TilesSmem &S, ui
   // barrier) ahead of other workgroups' mask / position phases -- each workgroup then returns
   // its slot to the DMA sooner (10 GiB: 2.24-2.31 -> 2.09 ms)
   __builtin_amdgcn_s_setprio(3);
-  stage_tile<true>(p, t, (u32)(size_t)(lds_u8 *)raw, wid, lane);
+  stage_tile_at<true>(tile0, llen, !nofront, (u32)(size_t)(lds_u8 *)raw, wid, lane, plane);
   __builtin_amdgcn_s_setprio(0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   TILES_STAMP(0);
   // the last wave also collects the newlines past the tile: the straggler at the next barrier,
   // so it goes first
-  if (wid == SNW - 1) __builtin_amdgcn_s_setprio(1);
-  const u64 tlo = t * TILE;
-  const u64 thi = (tlo + TILE < p.n) ? tlo + TILE : p.n;
-  const u32 tlen = (u32)(thi - tlo);
-  const u32 llen = (u32)(((tlo + TILE + SHALO < p.end) ? tlo + TILE + SHALO : p.end) - tlo);
-  if (llen < (u32)(TILE + SHALO) || (t == 0 && p.front < FRONT)) {  // slab end / file start: zero-fill
+  if (pwid == SNW - 1) __builtin_amdgcn_s_setprio(1);
+  if (llen < (u32)(TILE + SHALO) || nofront) {  // slab end / file start: zero-fill
     lds_barrier();  // (every wave's DMA landed: the fill may touch any part of the slot)
     for (u32 c = (u32)tid; c < (u32)((TILE + SHALO) / 16); c += SNT) {
       const u32 o = c * 16;
@@ -1079,14 +1147,13 @@ __device__ __forceinline__ void tiles_iter(const SlabParams &p, TilesSmem &S, ui
       if (o < llen) {
         v = keep_bytes(*reinterpret_cast<const uint4 *>(raw + FRONT + o), llen - o);
         if (llen & 3u) {
-          u32 ll;
-          const auto rs = tile_rsrc(p, t, ll);
+          const auto rs = tile_rsrc_at(tile0, llen);
           patch_tail(v, o, llen, tail_dword(rs, llen));
         }
       }
       *reinterpret_cast<uint4 *>(raw + FRONT + o) = v;
     }
-    if (t == 0 && p.front < FRONT && tid == 0) *reinterpret_cast<uint4 *>(raw) = make_uint4(0, 0, 0, 0);
+    if (nofront && ptid == 0) *reinterpret_cast<uint4 *>(raw) = make_uint4(0, 0, 0, 0);
     lds_barrier();
   }
   // ---- P2: '\n' mask word per thread (swizzled 16-byte reads), block count ----------------
@@ -1109,8 +1176,8 @@ __device__ __forceinline__ void tiles_iter(const SlabParams &p, TilesSmem &S, ui
   // ballot scan of the small per-lane counts, the wave totals read as scalars, a word's first two
   // positions without the loop, the halo words by the 3-op equality flags; round 5, within noise)
   const u32 incl = wave_scan_add_small(c);
-  if (lane == 63) S.wtot[wid] = incl;
-  if (tid == 0) { S.ndefer = 0; S.slow = 0; }
+  if (plane == 63) S.wtot[(u32)tid >> 6] = incl;  // (the address in a vector register: scalar ones are short)
+  if (ptid == 0) { S.ndefer = 0; S.slow = 0; }
   lds_barrier();
   TILES_STAMP(1);
   static_assert(SNW == 4, "the wave totals: one uniform 16-byte LDS read");
@@ -1118,7 +1185,7 @@ __device__ __forceinline__ void tiles_iter(const SlabParams &p, TilesSmem &S, ui
   const u32 t0 = (u32)__builtin_amdgcn_readfirstlane((int)w4.x), t1 = (u32)__builtin_amdgcn_readfirstlane((int)w4.y),
             t2 = (u32)__builtin_amdgcn_readfirstlane((int)w4.z), t3 = (u32)__builtin_amdgcn_readfirstlane((int)w4.w);
   const u32 T = t0 + t1 + t2 + t3;
-  const u32 wpre = (wid > 0 ? t0 : 0u) + (wid > 1 ? t1 : 0u) + (wid > 2 ? t2 : 0u);
+  const u32 wpre = (pwid > 0 ? t0 : 0u) + (pwid > 1 ? t1 : 0u) + (pwid > 2 ? t2 : 0u);
   // ---- P3: newline positions (tile + the first NLHALO past it), phase, validation -----------
   const bool use_arr = T + NLHALO <= (u32)SNLCAP;
   if (use_arr) {
@@ -1133,7 +1200,7 @@ __device__ __forceinline__ void tiles_iter(const SlabParams &p, TilesSmem &S, ui
       S.nlpos[o++] = (uint16_t)((u32)tid * 64 + ctz64(mm));
       mm &= mm - 1;
     }
-    if (wid == SNW - 1) {
+    if (pwid == SNW - 1) {
       const u32 wb = tlen >> 6;
       u32 hc = 0;
       u64 hm = 0;
@@ -1149,7 +1216,7 @@ __device__ __forceinline__ void tiles_iter(const SlabParams &p, TilesSmem &S, ui
           for (int j = 0; j < 4; ++j)
             hm |= (u64)eq16(*reinterpret_cast<const uint4 *>(raw + FRONT + wd * 64 + 16 * j), '\n') << (16 * j);
         }
-        if (wd == wb) hm &= ~lowmask(tlen & 63);
+        if (plane == 0) hm &= ~lowmask(tlen & 63);  // (wd == wb)
         if (wd * 64 + 64 > llen) hm &= lowmask(llen - wd * 64);
         hc = popc64(hm);
       }
@@ -1160,21 +1227,26 @@ __device__ __forceinline__ void tiles_iter(const SlabParams &p, TilesSmem &S, ui
         ++o2;
         hm &= hm - 1;
       }
-      if (lane == 63) S.nh = hpre < (u32)NLHALO ? hpre : (u32)NLHALO;
+      if (plane == 63) S.nh = hpre < (u32)NLHALO ? hpre : (u32)NLHALO;
     }
   }
   lds_barrier();
   TILES_STAMP(2);
-  const bool fs = p.file_start && t == 0;
+  bool fs = false;  // the file's first tile
   const u32 TT = use_arr ? T + S.nh : 0;
   u32 gi0;
-  if (t == 0) gi0 = (u32)((3 - (p.state_in & 3)) & 3);  // slab start: rank known
-  else if (use_arr && (wid == 0 || (T + 3) / 4 + 1 > 64u * (u32)wid)) gi0 = fq_guess_at(raw, S.nlpos, TT, lane);
-  else gi0 = GUESS_NONE;  // (or this wave has no records to certify: only wave 0's gi0 is kept)
+  if (t == 0) {  // slab start: rank known
+    const KArgs k = kargs();
+    fs = k->file_start != 0;
+    gi0 = (u32)((3 - (k->state_in & 3)) & 3);
+  } else if (use_arr && (pwid == 0 || (T + 3) / 4 + 1 > 64u * (u32)pwid)) {
+    gi0 = fq_guess_at(raw, S.nlpos, TT, lane, plane);
+  } else {
+    gi0 = GUESS_NONE;  // (or this wave has no records to certify: only wave 0's gi0 is kept)
+  }
   const u32 ng = gi0 < T ? (T - gi0 + 3) / 4 : 0;
   const u32 nrec = ng + (fs ? 1u : 0u);
   const bool slow = !use_arr || gi0 == GUESS_NONE || nrec > (u32)RCAP;
-  u32 *tdef = fq_defer(p, t);
   __builtin_amdgcn_s_setprio(2);
   if (!slow) {
     // record q = 64 w + lane (a tile's ~50 records fit one wave); one LDS round per step
@@ -1247,18 +1319,22 @@ __device__ __forceinline__ void tiles_iter(const SlabParams &p, TilesSmem &S, ui
       const bool dontcare = known && !good && e0 == s0 && r[s0 - 1] == '\n' && r[s0 - 2] == '\n' &&
                             r[s0 - 3] == '\n' && r[s0 - 4] == '\n';
       if (!act) continue;
-      fq_put(p, S, t, j, L, (uint16_t)(s0 | (good ? 0u : FQ_UNCERT)));
+      fq_put(S, t, j, L, (uint16_t)(s0 | (good ? 0u : FQ_UNCERT)));
       if (kSpans && good) {  // the record's inner line ends for the filters' spans (0xFFFF: trim the ID globally)
-        uint16_t *ln = p.fq_lines + t * (3 * RCAP) + 3 * L;
+        uint16_t *ln = p.fq_lines + (u64)t * (3 * RCAP) + 3 * L;
         ln[0] = (uint16_t)(idclean ? (e0 | ((crs & 1u) << 15)) : 0xFFFFu);
         ln[1] = (uint16_t)(e1 | ((crs & 2u) << 14));
         ln[2] = (uint16_t)(e2 | ((crs & 4u) << 13));
       }
-      if (L + 1 == nrec && known) fq_put(p, S, t, j, nrec, (uint16_t)(e3 + 1));  // the end of the tile's last record
+      if (L + 1 == nrec && known) fq_put(S, t, j, nrec, (uint16_t)(e3 + 1));  // the end of the tile's last record
       if (!good && !dontcare) {  // anything but a certified record: k_fixup validates it from global memory
         const u32 slot = atomicAdd(&S.ndefer, 1u);
-        if (slot < (u32)MAX_DEFER) { tdef[slot] = L; tdef[MAX_DEFER + slot] = s0; }
-        else S.slow = 1;
+        if (slot < (u32)MAX_DEFER) {
+          u32 *tdef = kargs()->tile_words + (u64)t * (2 * MAX_DEFER);  // (fq_defer)
+          tdef[slot] = L; tdef[MAX_DEFER + slot] = s0;
+        } else {
+          S.slow = 1;
+        }
       }
     }
   }
@@ -1272,21 +1348,23 @@ __device__ __forceinline__ void tiles_iter(const SlabParams &p, TilesSmem &S, ui
     // the batch's lines and words leave together after its last tile, from wave 0 (the next
     // batch writes slot 0 only after two more barriers); the lines are read once, by k_fq_place:
     // non-temporal.  (A slow or empty tile's line is never read.)
-    if (tid == 0) S.words[j] = word;
-    if (flush && wid == 0) {
+    if (ptid == 0) S.words[j] = word;
+    if (flush && pwid == 0) {
+      const KArgs k = kargs();
+      uint16_t *lines = reinterpret_cast<uint16_t *>(k->tile_stage);
+      u64 *aggs = k->tile_agg;
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       const u64 t0 = t - j;
       for (u32 c = (u32)lane; c < (j + 1) * (FQ_LINE_E / 8); c += 64) {
         const v4u v = *reinterpret_cast<const v4u *>(&S.line[0][0] + 8 * c);
-        __builtin_nontemporal_store(v, (__attribute__((address_space(1))) v4u *)(reinterpret_cast<uint16_t *>(p.tile_stage) +
-                                                                                 t0 * FQ_LINE_E + 8 * c));
+        __builtin_nontemporal_store(v, (__attribute__((address_space(1))) v4u *)(lines + t0 * FQ_LINE_E + 8 * c));
       }
       if ((u32)lane * 2 < j + 1) {  // the words, 16 bytes per lane (a last odd word alone)
         if ((u32)lane * 2 + 1 < j + 1) {
           const v4u v = *reinterpret_cast<const v4u *>(&S.words[2 * lane]);
-          *(__attribute__((address_space(1))) v4u *)(p.tile_agg + t0 + 2 * lane) = v;
+          *(__attribute__((address_space(1))) v4u *)(aggs + t0 + 2 * lane) = v;
         } else {
-          p.tile_agg[t0 + 2 * lane] = S.words[2 * lane];
+          aggs[t0 + 2 * lane] = S.words[2 * lane];
         }
       }
     }
@@ -1299,7 +1377,11 @@ __device__ __forceinline__ void tiles_iter(const SlabParams &p, TilesSmem &S, ui
 // certified and stored before the next is DMA'd; 7 workgroups per CU keep the DMA busy); no waits
 // on other workgroups, so the grid need not be co-resident.
 #ifndef SIDX_TILES_WGS
-#define SIDX_TILES_WGS 7  // 19.5 KiB of LDS: 8 would fit, but at <= 64 VGPRs (41 SGPR spills) it ran 1.6 % slower
+// 7: 21.2 KiB of LDS.  8 per CU needs bursts of 4 tiles (SIDX_FQ_BLK=4: 19.6 KiB) and 64 VGPRs, which the
+// compiler meets -- but at eight waves per SIMD it allots 80 SGPRs, not 102, and spills 8 again; with those
+// spills the arm ran 0.2-2.5 % faster than 7 per CU (DESIGN.md §3 "Registers of the tile loop"): not adopted
+// before the loop is spill-free there too (tests/test_tile_kernel_resources.py holds the product's budget)
+#define SIDX_TILES_WGS 7
 #endif
 template <bool kSpans>
 __global__ __launch_bounds__(SNT, SIDX_TILES_WGS) void k_fq_tiles(const SlabParams p) {
@@ -1321,9 +1403,9 @@ __global__ __launch_bounds__(SNT, SIDX_TILES_WGS) void k_fq_tiles(const SlabPara
   // than 32.  The claims keep that order and hand it out by a counter (claim_loop): no workgroup
   // is left with a twelfth batch while others have finished their eleventh, and one that falls
   // behind takes fewer (DESIGN.md §3 "Tile order").
-  claim_loop(p, S.pad, tid, [&](u32 t, const ClaimRange &r) {
+  claim_loop(S.pad, tid, [&](u32 t, const ClaimRange &r, const ClaimBytes &cb) {
     const u32 j = (t - r.tb) & (FQ_BLK - 1);  // (bursts start at even tiles: the words leave 16 bytes per lane)
-    tiles_iter<kSpans>(p, S, raw, t, tid, lane, wid, tacc, j, j == FQ_BLK - 1 || t + 1 == r.te);
+    tiles_iter<kSpans>(p, cb, t - r.tb, S, raw, t, tid, lane, wid, tacc, j, j == FQ_BLK - 1 || t + 1 == r.te);
     ++ntl;
   });
   if (tacc) {  // per workgroup: wave 0's phases in slots 0-5, wave 1's in the next 9-slot record
@@ -2123,23 +2205,26 @@ __device__ __forceinline__ u32 fa_check(const uint8_t *r, const u64 *mnl, u32 lo
   return part ? FA_DEFER : FA_INV;
 }
 
-__device__ __forceinline__ void fa_iter(const SlabParams &p, FaSmem &S, uint8_t *raw, u64 t, int tid, int lane,
-                                        int wid) {
+__device__ __forceinline__ void fa_iter(const SlabParams &p, const ClaimBytes &cb, u32 rel, FaSmem &S, uint8_t *raw,
+                                        u32 t, int tid, int lane, int wid) {
+  // (predicates only: addresses use tid / lane; one copy, the kernel has no vector register to spare)
+  int ptid = tid;
+  asm volatile("" : "+v"(ptid));
+  const int plane = ptid & 63;
+  const u32 tlen = cb.tlen(rel), llen = cb.llen(rel);
+  const uint8_t *tile0 = cb.base + rel * (u32)TILE;
   __builtin_amdgcn_s_setprio(3);  // as k_fq_tiles: DMA issue, then the certification, first
-  stage_tile<false>(p, t, (u32)(size_t)(lds_u8 *)raw, wid, lane);  // the tile alone: no halo, no front
+  // the tile alone: no halo, no front
+  stage_tile_at<false>(tile0, llen, !tile_nofront(t), (u32)(size_t)(lds_u8 *)raw, wid, lane, plane);
   __builtin_amdgcn_s_setprio(0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // a wave classifies only the bytes it staged
-  if (tid == 0) S.finv = FA_NONE;
-  const u64 tlo = t * TILE;
-  const u32 tlen = (u32)(((tlo + TILE < p.n) ? tlo + TILE : p.n) - tlo);
-  const u32 llen = (u32)(((tlo + TILE + SHALO < p.end) ? tlo + TILE + SHALO : p.end) - tlo);
+  if (ptid == 0) S.finv = FA_NONE;
   if (llen < (u32)TILE && (llen & 3u)) {  // slab end: the partial last dword came back as zeros
     lds_barrier();
-    if (tid == 0) {
+    if (ptid == 0) {
       const u32 o = llen & ~15u;
       uint4 v = keep_bytes(*reinterpret_cast<const uint4 *>(raw + FRONT + o), llen - o);
-      u32 ll;
-      const auto rs = tile_rsrc(p, t, ll);
+      const auto rs = tile_rsrc_at(tile0, llen);
       patch_tail(v, o, llen, tail_dword(rs, llen));
       *reinterpret_cast<uint4 *>(raw + FRONT + o) = v;
     }
@@ -2191,7 +2276,7 @@ __device__ __forceinline__ void fa_iter(const SlabParams &p, FaSmem &S, uint8_t 
   const u32 cond = (GTx == 0 && NLx == 0 && (u & (0ull - u) & gt)) ? 1u : 0u;
   const u32 incl = wave_scan_add(c);
   const bool wcond = __ballot(cond) != 0;
-  if (lane == 63) {
+  if (plane == 63) {
     S.wagg[wid] = incl | (wcond ? 1u << 20 : 0u);
     S.wlast[wid] = GTi;
     S.wnl[wid] = NLi;
@@ -2239,12 +2324,17 @@ __device__ __forceinline__ void fa_iter(const SlabParams &p, FaSmem &S, uint8_t 
   // ---- validation of the pieces that close at the candidates -------------------------------
   __builtin_amdgcn_s_setprio(2);
   const bool slow = ncand > (u32)RCAP;
-  uint16_t *stage = reinterpret_cast<uint16_t *>(p.tile_stage + t * RCAP);  // position | status << 14
+  uint16_t *stage = reinterpret_cast<uint16_t *>(p.tile_stage + (u64)t * RCAP);  // position | status << 14
   // A slab after the file's first: its first tile's first boundary (the incoming state is known
   // there) closes the record open at the slab start, which the previous slab owns and checks
   // through its halo; any other piece starting before data[0] is checked as a part (never INV).
-  const bool own0 = p.file_start || t != 0;
-  const u32 skip0 = own0 ? ~0u : ((delta && !(p.state_in & 1)) ? 1u : 0u);
+  bool fs = false;  // the file's first tile
+  u32 skip0 = ~0u;
+  if (t == 0) {
+    const KArgs k = kargs();
+    fs = k->file_start != 0;
+    if (!fs) skip0 = (delta && !(k->state_in & 1)) ? 1u : 0u;
+  }
   if (!slow) {
     for (u32 i = (u32)tid; i < ncand; i += SNT) {
       const u32 c = S.cand[i];
@@ -2252,13 +2342,12 @@ __device__ __forceinline__ void fa_iter(const SlabParams &p, FaSmem &S, uint8_t 
       u32 st;
       if (i == skip0) st = FA_SKIP;
       else if (i == 0 && delta) st = FA_DEFER;  // conditional: its piece has no '\n' in this tile
-      else st = fa_check(r, S.mnl, lo, g, lo == 0 && (t != 0 || !p.file_start));
+      else st = fa_check(r, S.mnl, lo, g, lo == 0 && !fs);
       stage[i] = (uint16_t)(g | (st << 14));
       if (st == FA_INV) atomicMin(&S.finv, i);
     }
   }
-  u32 *tw = p.tile_words + t * FAW;
-  if (tid == SNT - 1) {  // the certificate of the piece open at the tile's end (fa_w_tcert)
+  if (ptid == SNT - 1) {  // the certificate of the piece open at the tile's end (fa_w_tcert)
     // (the first '\n' after the last '>': two mask words in one LDS round, the loop beyond)
     const u32 wi = alast >> 6;
     const u64 w0 = wi < (u32)(TILE / 64) ? S.mnl[wi] & (~0ull << (alast & 63)) : 0ull;
@@ -2267,11 +2356,14 @@ __device__ __forceinline__ void fa_iter(const SlabParams &p, FaSmem &S, uint8_t 
     if (q > tlen) q = tlen;
     S.tcert = (q > alast && q + 1 < tlen && ascii_nonspace(r[q - 1]) && ascii_nonspace(r[q + 1])) ? 1u : 0u;
   }
-  if (t == p.ntiles - 1 && tid == SNT - 1) {  // EOF piece [last '>' + 1, n), fasta.go:111 + :123-125
+  if (cb.nrel - rel * (u32)TILE <= (u32)TILE && ptid == SNT - 1) {  // the slab's last tile: the EOF piece
+    // [last '>' + 1, n), fasta.go:111 + :123-125
+    const KArgs k = kargs();
+    u32 *tw = k->tile_words + (u64)t * FAW;
     u32 est = FA_OK;  // a slab with a halo: its last record is closed there (k_fa_fixup)
     const u32 lo = alast;
-    if (p.end > p.n || !p.eof) {
-    } else if (lo != 0 || (t == 0 && p.file_start)) {
+    if (k->end > k->n || !k->eof) {
+    } else if (lo != 0 || fs) {
       if (tlen > lo + 1 && fa_find_nl(S.mnl, lo, tlen) < tlen) est = fa_check(r, S.mnl, lo, tlen, false);
     } else {
       est = fa_check(r, S.mnl, 0, tlen, true);
@@ -2285,8 +2377,9 @@ __device__ __forceinline__ void fa_iter(const SlabParams &p, FaSmem &S, uint8_t 
     const u32 finv = S.finv;
     const u64 word = fa_word(A, ncand, slow, delta, delta ? (S.cand[0] & 0x3FFFu) : FA_NONE,
                              (A >> 3) ? (S.cand[delta] & 0x3FFFu) : FA_NONE, finv != FA_NONE, S.tcert != 0);
-    if (tid == 0) p.tile_agg[t] = word;
-    if (tid == 0 && finv != FA_NONE) {
+    if (ptid == 0) p.tile_agg[t] = word;
+    if (ptid == 0 && finv != FA_NONE) {
+      u32 *tw = kargs()->tile_words + (u64)t * FAW;
       tw[4] = finv;
       tw[5] = S.cand[finv] >> 14;
     }
@@ -2298,7 +2391,10 @@ __device__ __forceinline__ void fa_iter(const SlabParams &p, FaSmem &S, uint8_t 
 // dealt round-robin ran 1.858-1.994 ms against 1.896-2.020 for single tiles in XCD-major
 // grid-stride order (round 5)
 #ifndef SIDX_FA_WGS
-#define SIDX_FA_WGS 7  // 19.1 KiB of LDS (no halo in the slot); 8 per CU (<= 64 VGPRs) measured the same
+// the compiler's bound; the grid follows the occupancy query (tile_grid): 19.1 KiB of LDS (no halo in the slot)
+// and 63 VGPRs let 8 workgroups per CU in.  Held at 7 per CU the pass ran between 1.6 % faster and 6 % slower
+// than at 8, the 8-per-CU contexts differing more among themselves (DESIGN.md §3 "Registers of the tile loop")
+#define SIDX_FA_WGS 7
 #endif
 __global__ __launch_bounds__(SNT, SIDX_FA_WGS) void k_fa_tiles(const SlabParams p) {
   __shared__ __attribute__((aligned(16))) uint8_t raw[FRONT + TILE];
@@ -2306,7 +2402,9 @@ __global__ __launch_bounds__(SNT, SIDX_FA_WGS) void k_fa_tiles(const SlabParams 
   if (gated_off(p)) return;  // format speculation failed: the host re-runs with the detected format
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  claim_loop(p, S.pad[0], tid, [&](u32 t, const ClaimRange &) { fa_iter(p, S, raw, t, tid, lane, wid); });
+  claim_loop(S.pad[0], tid, [&](u32 t, const ClaimRange &r, const ClaimBytes &cb) {
+    fa_iter(p, cb, t - r.tb, S, raw, t, tid, lane, wid);
+  });
 }
 
 // first boundary of tile u given its words and entering state: the conditional '>' when the

@@ -121,13 +121,16 @@ __device__ __forceinline__ void dma_body4(u32 voff, u32 lds, __amdgpu_buffer_rsr
                  "s_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(lds), "s"(rs) : "memory");
 }
+// stage_tile_at: the tile at `tile0` (its byte 0) with llen readable bytes from there on (at most
+// TILE + SHALO); `shifted`: FRONT bytes are readable in front of it.  Only 32-bit values besides
+// the base, all wave-uniform: what a claim loop keeps per tile (sidx_kernels.hip, ClaimBytes).
+// plane: the lane number the predicates use (the claim loops pass an opaque copy, so that no
+// predicate is kept in scalar registers from tile to tile).
 template <bool kFq>
-__device__ __forceinline__ void stage_tile(const SlabParams &p, u64 tn, u32 dst, int wid, int lane) {
-  const u64 tlo = tn * TILE;
-  const bool shifted = tlo >= FRONT || p.front >= FRONT;
-  const u64 ba = (u64)(p.data + tlo) - (shifted ? FRONT : 0);
-  const u64 lim = (tlo + TILE + SHALO < p.end) ? tlo + TILE + SHALO : p.end;
-  const u32 nrec = (u32)(lim - tlo) + (shifted ? FRONT : 0);
+__device__ __forceinline__ void stage_tile_at(const uint8_t *tile0, u32 llen, bool shifted, u32 dst, int wid, int lane,
+                                              int plane) {
+  const u64 ba = (u64)tile0 - (shifted ? FRONT : 0);
+  const u32 nrec = llen + (shifted ? FRONT : 0);
   const uint8_t *sbase = (const uint8_t *)(((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)ba)) |
                                            ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(ba >> 32)) << 32));
   const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)sbase, (short)0,
@@ -144,13 +147,20 @@ __device__ __forceinline__ void stage_tile(const SlabParams &p, u64 tn, u32 dst,
     }
   }
   if (!kFq) return;
-  if (wid == 0 && lane < FRONT / 4) dma_piece4((u32)lane * 4u - adj, dst, rs);
+  if (wid == 0 && plane < FRONT / 4) dma_piece4((u32)lane * 4u - adj, dst, rs);
+  constexpr bool kAllPieces = SNW * SHPW == HALO / 256;  // every wave's pieces exist
 #pragma unroll
   for (int h = 0; h < SHPW; ++h) {
     const int piece = wid * SHPW + h;
     const u32 h0 = (u32)(FRONT + TILE) + (u32)piece * 256u;
-    if (piece < HALO / 256) dma_piece4(h0 + (u32)lane * 4u - adj, dst + h0, rs);
+    if (kAllPieces || piece < HALO / 256) dma_piece4(h0 + (u32)lane * 4u - adj, dst + h0, rs);
   }
+}
+template <bool kFq>
+__device__ __forceinline__ void stage_tile(const SlabParams &p, u64 tn, u32 dst, int wid, int lane) {
+  const u64 tlo = tn * TILE;
+  const u64 lim = (tlo + TILE + SHALO < p.end) ? tlo + TILE + SHALO : p.end;
+  stage_tile_at<kFq>(p.data + tlo, (u32)(lim - tlo), tlo >= FRONT || p.front >= FRONT, dst, wid, lane, lane);
 }
 
 }  // namespace sidx
