@@ -393,7 +393,8 @@ class Context:
 
     # -- download filters (node/filter/) -------------------------------------------------------
     def filter_device(self, name: str, d_data: int, n: int, d_out: int, out_cap: int) -> SubsetResult:
-        """fq2fa / anonymize over a FASTQ section in HBM (count = records, size = bytes out)."""
+        """fq2fa over a FASTQ section, anonymize over a FASTQ, FASTA or SAM section (the format is
+        detected first) in HBM (count = records, size = bytes out; ESPACE: size = the bytes needed)."""
         r = L.SubsetResult()
         rc = self._lib.shockidx_filter_device(self._h, name.encode(), d_data, n, d_out, out_cap, ctypes.byref(r))
         return _sub_result(r, rc)

@@ -1,7 +1,8 @@
 """Direct access to the launchers behind the public entry points, for tests that need counts or
 counters no input file of test size produces: the device-wide scans (sidx_scan.hpp through
-sidx_scan_flags / sidx_scan_u64 / sidx_scan_max_u64 / sidx_crs_scan) and the FASTQ filter writer
-(sidx_filter.hip through sidx_filter_spans / sidx_filter_write).  Every launcher returns hipError_t
+sidx_scan_flags / sidx_scan_u64 / sidx_scan_max_u64 / sidx_crs_scan), the FASTQ filter writer
+(sidx_filter.hip through sidx_filter_spans / sidx_filter_write) and the FASTA boundary scan of anonymize
+(sidx_filter.hip through sidx_fa_bnd_count / sidx_fa_bnd_write).  Every launcher returns hipError_t
 as an int (0: success).  All launches go to ctx.stream; buffers come from ctx.alloc.
 
 A launcher trusts its caller, so every helper here asserts the launcher's preconditions on the host
@@ -17,6 +18,11 @@ before it launches -- a mistake in a test fails in Python and never reaches the 
   write    spans() ran and every span lies inside its record; outoff is the exact exclusive sum of
            the downloaded outlen; wfirst has total / block + 4 words; out has total + 64 bytes, is
            16-byte aligned and is filled with 0xAB before the launch
+  fa bnd   data comes from ctx.alloc(n + 64), n >= 1; with nt = ceil(n / TILE) tiles, lnl / lgt / cnl / cgt /
+           tcnt / toff hold nt + 1 words each and slot sidx_fa_slot() * (nt + 1) u16s; tmp holds the queried
+           size; for the write, tcnt / toff are what the count left (checked against the reference first: a
+           wrong count never reaches the writer) and B holds K = toff[nt-1] + tcnt[nt-1] words, K at most
+           the number of '>' in data, followed by guard words of 0xAB
 """
 import ctypes
 
@@ -37,6 +43,11 @@ _PROTOS = {
     "sidx_scan_small_items": (_u64, []),
     "sidx_filter_block": (_u64, []),
     "sidx_filter_recs": (ctypes.c_uint32, []),
+    "sidx_fa_slot": (ctypes.c_uint32, []),
+    # (data, n, lnl, lgt, cnl, cgt, tcnt, toff, slot, tmp, tmp_bytes, stream)
+    "sidx_fa_bnd_count": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _psz, _vp]),
+    # (data, n, cnl, cgt, tcnt, toff, slot, B, stream)
+    "sidx_fa_bnd_write": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # (in, out, n, tmp, tmp_bytes, stream)
     "sidx_scan_flags": (_i32, [_vp, _vp, _u64, _vp, _psz, _vp]),
     "sidx_scan_u64": (_i32, [_vp, _vp, _u64, _vp, _psz, _vp]),
@@ -307,6 +318,70 @@ class WriterCase:
         self.ctx.sync()
         nblocks = (total + block - 1) // block
         return d_out.download(total + GUARD).tobytes(), download(d_wf, np.uint64, nblocks)
+
+    def free(self):
+        for b in self.bufs:
+            b.free()
+        self.bufs = []
+
+
+# ---- the FASTA boundary scan (anonymize over a section whose record index fails) --------------------
+TILE = 16384  # SIDX_TILE
+
+
+def fa_slot() -> int:
+    return int(fn("sidx_fa_slot")())
+
+
+class FaBoundaryJob:
+    """One buffer through sidx_fa_bnd_count (k_fa_last, the two max scans, k_fa_bnd, the sum scan) and
+    sidx_fa_bnd_write (k_fa_bwrite).  count() -> (tcnt[nt], toff[nt], slot[nt, FSLOT]); write(K) -> B with
+    its guard words.  The guard is a whole tile of words: every '>' of a last tile, were they all
+    written past the end, still lands inside the allocation."""
+    BGUARD = TILE
+
+    def __init__(self, ctx, data):
+        a = np.ascontiguousarray(data)
+        assert a.dtype == np.uint8 and a.ndim == 1 and len(a) >= 1
+        self.ctx, self.n, self.nt = ctx, len(a), (len(a) + TILE - 1) // TILE
+        self.ngt = int((a == 0x3E).sum())
+        self.d_data = upload(ctx, a, 64)  # the loads may run 64 bytes past the buffer
+        w = self.nt + 1
+        self.words = [filled(ctx, 8 * w, 0xAB) for _ in range(6)]  # lnl lgt cnl cgt tcnt toff
+        self.d_slot = filled(ctx, 2 * fa_slot() * w, 0xAB)
+        sb = ctypes.c_size_t(0)
+        rc = fn("sidx_fa_bnd_count")(None, self.n, None, None, None, None, None, None, None, None, ctypes.byref(sb), ctx.stream)
+        assert rc == HIP_SUCCESS and sb.value >= 16, (rc, sb.value)
+        self.need = int(sb.value)
+        self.d_tmp = ctx.alloc(self.need)
+        self.bufs = [self.d_data, self.d_slot, self.d_tmp] + self.words
+        self.K = None
+
+    def count(self):
+        w = self.nt + 1
+        assert self.d_data.nbytes >= self.n + 64 and all(b.nbytes >= 8 * w for b in self.words)
+        assert self.d_slot.nbytes >= 2 * fa_slot() * w and self.d_tmp.nbytes >= self.need and self.d_tmp.ptr % 16 == 0
+        sb = ctypes.c_size_t(self.need)
+        rc = fn("sidx_fa_bnd_count")(self.d_data.ptr, self.n, *[b.ptr for b in self.words], self.d_slot.ptr, self.d_tmp.ptr,
+                                     ctypes.byref(sb), self.ctx.stream)
+        assert rc == HIP_SUCCESS, rc
+        self.ctx.sync()
+        tcnt, toff = download(self.words[4], np.uint64, self.nt), download(self.words[5], np.uint64, self.nt)
+        slot = download(self.d_slot, np.uint16, fa_slot() * self.nt).reshape(self.nt, fa_slot())
+        return tcnt, toff, slot
+
+    def write(self, K: int):
+        """K: toff[nt-1] + tcnt[nt-1] of a count() the caller has compared with the reference."""
+        assert 0 <= K <= self.ngt, (K, self.ngt)
+        self.K = K
+        d_B = filled(self.ctx, 8 * (K + self.BGUARD), 0xAB)
+        self.bufs.append(d_B)
+        assert d_B.nbytes >= 8 * (K + self.BGUARD)
+        rc = fn("sidx_fa_bnd_write")(self.d_data.ptr, self.n, self.words[2].ptr, self.words[3].ptr, self.words[4].ptr,
+                                     self.words[5].ptr, self.d_slot.ptr, d_B.ptr, self.ctx.stream)
+        assert rc == HIP_SUCCESS, rc
+        self.ctx.sync()
+        return download(d_B, np.uint64, K + self.BGUARD)
 
     def free(self):
         for b in self.bufs:
