@@ -48,7 +48,8 @@ extern "C" {
  *    SHOCKIDX_ESPACE (4 returned SHOCKIDX_EINVAL); whole-file builds check their own table's
  *    end invariants (SHOCKIDX_EINTERNAL instead of a short table).
  *    Added since without a version change (purely additive): shockidx_column_device,
- *    shockidx_column_fd, shockidx_stream_filter_device, shockidx_download_plan */
+ *    shockidx_column_fd, shockidx_stream_filter_device, shockidx_download_plan,
+ *    shockidx_stream_last_stats */
 #define SHOCKIDX_ABI_VERSION 5
 
 /* index kinds = the registry keys served (index/index.go:21-28) */
@@ -381,12 +382,26 @@ int shockidx_filter_device(shockidx_ctx *ctx, const char *filter, const void *d_
  * SHOCKIDX_EINVAL and nothing is written: the reference's SectionReader would see a short read
  * there, and a valid index never produces such a row.  filter NULL or "" is the Streamer without a
  * Filter (:88-90): shockidx_subset_gather of the sections.  d_data and d_out 16-byte aligned.
- * Sections of at most SHOCKIDX_STREAM_SMALL bytes (environment; default 1 MiB) that are FASTQ are
- * indexed together, in a number of launches and host waits that does not grow with their number;
- * the others go through the single-section filter one at a time. */
+ * Small sections -- at most SHOCKIDX_STREAM_SMALL bytes (environment, applies to every format; the
+ * defaults are per format, DESIGN.md "The sectioned stream") and FASTQ, FASTA or SAM (as detected per
+ * section under anonymize; fq2fa reads everything as FASTQ) -- are indexed together, every maximal run
+ * of consecutive small sections of one format in a number of launches and host waits that does not
+ * grow with the run's length; the others (too long, or of no detected format) go through the
+ * single-section filter one at a time. */
 int shockidx_stream_filter_device(shockidx_ctx *ctx, const char *filter, const void *d_data, uint64_t data_len,
                                   const void *d_secs, uint64_t nsecs, void *d_out, uint64_t out_cap,
                                   int64_t *err_section, shockidx_subset_result *result);
+
+/* Which path the context's last shockidx_stream_filter_device call with a filter took (the stream
+ * delivered does not depend on it). */
+typedef struct shockidx_stream_stats {
+  uint64_t sections;     /* nsecs of the context's last shockidx_stream_filter_device call with a filter */
+  uint64_t batches;      /* groups that took the segmented path (counted once, not per walk) */
+  uint64_t batched;      /* sections inside them */
+  uint64_t singles;      /* sections that went through the single-section filter */
+  uint64_t by_format[3]; /* batches of FASTQ, FASTA, SAM sections */
+} shockidx_stream_stats;
+int shockidx_stream_last_stats(const shockidx_ctx *ctx, shockidx_stream_stats *out);
 
 /* ---- The download plan: all parts of an index download in one call -------------------------
  * controller/node/single.go:372-483 builds the Streamer's section list (s.R) part by part: a request

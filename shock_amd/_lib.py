@@ -34,7 +34,8 @@ EXPORTS = ("shockidx_ctx_create", "shockidx_ctx_destroy", "shockidx_build_device
            "shockidx_subset_node",
            "shockidx_chunkrecord_device", "shockidx_chunkrecord_fd", "shockidx_chunkrecord_subset_device", "shockidx_create_subset_index",
            "shockidx_column_device", "shockidx_column_fd",
-           "shockidx_idx_part", "shockidx_idx_range", "shockidx_filter_device", "shockidx_stream_filter_device", "shockidx_download_plan", "shockidx_ctx_trim",
+           "shockidx_idx_part", "shockidx_idx_range", "shockidx_filter_device", "shockidx_stream_filter_device", "shockidx_stream_last_stats",
+           "shockidx_download_plan", "shockidx_ctx_trim",
            "shockidx_ctx_workspace_bytes", "shockidx_ctx_set_dev_cap", "shockidx_multi_create", "shockidx_multi_destroy", "shockidx_multi_rccl",
            "shockidx_multi_build_host", "shockidx_multi_build_fd", "shockidx_multi_create_index", "shockidx_multi_plan",
            "shockidx_multi_build_resident", "shockidx_device_count")
@@ -90,6 +91,12 @@ class SubsetResult(ctypes.Structure):
     @property
     def message(self) -> bytes:
         return ctypes.string_at(ctypes.addressof(self) + SubsetResult.err.offset, self.err_len)
+
+
+class StreamStats(ctypes.Structure):
+    """mirrors shockidx_stream_stats (include/shockidx.h)"""
+    _fields_ = [("sections", ctypes.c_uint64), ("batches", ctypes.c_uint64), ("batched", ctypes.c_uint64),
+                ("singles", ctypes.c_uint64), ("by_format", ctypes.c_uint64 * 3)]
 
 
 assert ctypes.sizeof(SlabSummary) == 64
@@ -203,6 +210,8 @@ def lib():
     L.shockidx_stream_filter_device.argtypes = [vp, ctypes.c_char_p, vp, u64, vp, u64, vp, u64,
                                                 ctypes.POINTER(ctypes.c_int64), PSub]
     L.shockidx_stream_filter_device.restype = i32
+    L.shockidx_stream_last_stats.argtypes = [vp, ctypes.POINTER(StreamStats)]
+    L.shockidx_stream_last_stats.restype = i32
     L.shockidx_download_plan.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), u64, vp, u64, ctypes.c_int64,
                                          vp, u64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp, u64,
                                          ctypes.POINTER(ctypes.c_int64), PSub]

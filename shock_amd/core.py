@@ -435,6 +435,18 @@ class Context:
         out.err_section = int(es.value)
         return out
 
+    def stream_stats(self) -> dict:
+        """Which path the last stream_filter_device call with a filter took (shockidx_stream_last_stats):
+        sections, batches (groups of small sections of one format that took the segmented path), batched
+        (sections inside them), singles (sections through the single-section filter) and by_format
+        (batches of FASTQ, FASTA, SAM sections)."""
+        st = L.StreamStats()
+        rc = self._lib.shockidx_stream_last_stats(self._h, ctypes.byref(st))
+        if rc != L.OK:
+            raise L.ShockIdxError(rc, "shockidx_stream_last_stats")
+        return {"sections": int(st.sections), "batches": int(st.batches), "batched": int(st.batched),
+                "singles": int(st.singles), "by_format": [int(v) for v in st.by_format]}
+
     def stream_filter_host(self, name, data, sections) -> SubsetResult:
         """Host-memory convenience: upload the node and the sections [(pos, len), ...], stream on the
         device, download (r.gathered = the bytes delivered, also before an error)."""

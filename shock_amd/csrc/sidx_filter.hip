@@ -537,13 +537,17 @@ __device__ void wave_nl(const uint8_t *d, u64 n, u64 lo, u64 hi, int lane, u64 &
 #else
 #define SIDX_FAS_ATTR
 #endif
+// SEG: the sectioned stream's flat sequences (sidx_stream.hip): B holds rows {start, B_k} (bstride 2), so
+// the start comes from the row and not from the boundary before, and the counter is ord[k] + 1 (the
+// sequence's ordinal within its section: the reader, and with it the counter, restarts at every section).
+template <bool SEG>
 __global__ __launch_bounds__(256) SIDX_FAS_ATTR void k_fa_anon_spans(const uint8_t *d, u64 n, const u64 *B, u64 bstride, u64 m,
-                                                       u64 *bspan, u64 *outlen, u64 *firstbad) {
+                                                       u64 *bspan, u64 *outlen, u64 *firstbad, const u32 *ord) {
   const int lane = threadIdx.x & 63;
   const u64 nw = (u64)gridDim.x * (blockDim.x / 64);
   for (u64 k = (u64)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); k < m; k += nw) {
-    u64 s = k ? B[(k - 1) * bstride] : 0;
-    const u64 e0 = B[k * bstride];
+    u64 s = SEG ? B[2 * k] : k ? B[(k - 1) * bstride] : 0;
+    const u64 e0 = SEG ? B[2 * k + 1] : B[k * bstride];
     // the common sequence in one round of loads (lanes 0-3: its first two and last two bytes):
     // '>' then a printable ASCII byte other than '>', and a printable last byte or a space after
     // one -- the serial '>' and TrimSpace loops below then stop at once (they cost ~8 dependent
@@ -584,7 +588,7 @@ __global__ __launch_bounds__(256) SIDX_FAS_ATTR void k_fa_anon_spans(const uint8
       } else {
         bspan[2 * k] = f + 1;
         bspan[2 * k + 1] = hi;
-        outlen[k] = 1 + ndigits(k + 1) + 1 + (hi - f - 1 - (c - 1)) + 1;
+        outlen[k] = 1 + ndigits(SEG ? (u64)ord[k] + 1 : k + 1) + 1 + (hi - f - 1 - (c - 1)) + 1;
       }
     }
   }
@@ -637,8 +641,10 @@ __device__ __forceinline__ void wave_sync_lds() {
 #else
 #define SIDX_FA_ATTR
 #endif
+// SEG: the counter of sequence k is ord[k] + 1 (k_fa_anon_spans<true>)
+template <bool SEG>
 __global__ __launch_bounds__(256) SIDX_FA_ATTR void k_fa_anon_write(const uint8_t *d, u64 n, const u64 *bspan, const u64 *outoff,
-                                                       u64 K, uint8_t *out) {
+                                                       u64 K, uint8_t *out, const u32 *ord) {
   constexpr int SK = SIDX_FA_STEPK;
   static_assert(SK >= 1 && SK <= 4, "16-bit count fields: at most four chunks per step");
   constexpr u64 STEP = 1024ull * SK;
@@ -649,7 +655,7 @@ __global__ __launch_bounds__(256) SIDX_FA_ATTR void k_fa_anon_write(const uint8_
   for (u64 k = (u64)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); k < K; k += nw) {
     const u64 obase = outoff[k];
     u64 blk = obase & ~15ull;  // output byte of stg[0]
-    const u64 id = k + 1;
+    const u64 id = SEG ? (u64)ord[k] + 1 : k + 1;
     const u32 nd = ndigits(id);
     const u32 h0 = (u32)(obase - blk);
     if (lane == 0) stg[h0] = '>';
@@ -842,12 +848,26 @@ extern "C" hipError_t sidx_fa_bnd_write(const uint8_t *d, u64 n, const u64 *cnl,
 static u32 wave_grid(u64 K) { return (u32)((K + 3) / 4 < 65536 ? (K + 3) / 4 : 65536); }
 extern "C" hipError_t sidx_fa_anon_spans(const uint8_t *d, u64 n, const u64 *B, u64 bstride, u64 m, u64 *bspan, u64 *outlen,
                                          u64 *firstbad, hipStream_t s) {
-  if (m) hipLaunchKernelGGL(k_fa_anon_spans, dim3(wave_grid(m)), dim3(256), 0, s, d, n, B, bstride, m, bspan, outlen, firstbad);
+  if (m) hipLaunchKernelGGL(k_fa_anon_spans<false>, dim3(wave_grid(m)), dim3(256), 0, s, d, n, B, bstride, m, bspan, outlen,
+                            firstbad, (const u32 *)nullptr);
   return hipGetLastError();
 }
 extern "C" hipError_t sidx_fa_anon_write(const uint8_t *d, u64 n, const u64 *bspan, const u64 *outoff, u64 K,
                                          uint8_t *out, hipStream_t s) {
-  if (K) hipLaunchKernelGGL(k_fa_anon_write, dim3(wave_grid(K)), dim3(256), 0, s, d, n, bspan, outoff, K, out);
+  if (K) hipLaunchKernelGGL(k_fa_anon_write<false>, dim3(wave_grid(K)), dim3(256), 0, s, d, n, bspan, outoff, K, out,
+                            (const u32 *)nullptr);
+  return hipGetLastError();
+}
+// the sectioned stream's flat sequences: rows {start, B_k}, ord: each one's ordinal within its section
+extern "C" hipError_t sidx_fa_anon_spans_seg(const uint8_t *d, u64 n, const u64 *rows, const u32 *ord, u64 m, u64 *bspan,
+                                             u64 *outlen, u64 *firstbad, hipStream_t s) {
+  if (m) hipLaunchKernelGGL(k_fa_anon_spans<true>, dim3(wave_grid(m)), dim3(256), 0, s, d, n, rows, (u64)2, m, bspan, outlen,
+                            firstbad, ord);
+  return hipGetLastError();
+}
+extern "C" hipError_t sidx_fa_anon_write_seg(const uint8_t *d, u64 n, const u64 *bspan, const u64 *outoff, const u32 *ord,
+                                             u64 K, uint8_t *out, hipStream_t s) {
+  if (K) hipLaunchKernelGGL(k_fa_anon_write<true>, dim3(wave_grid(K)), dim3(256), 0, s, d, n, bspan, outoff, K, out, ord);
   return hipGetLastError();
 }
 extern "C" hipError_t sidx_sam_anon_spans(const uint8_t *d, u64 n, const u64 *rows, u64 K, u64 *span, u64 *outlen,

@@ -124,6 +124,7 @@ struct shockidx_ctx {
   Buf<uint8_t> d_colb{bufs};       //   flags, ranks, key spans, scan workspace (bytes)
   Buf<uint8_t> d_plan{bufs};       // download plan: the level-2 workspace of CHUNK_RANGE (level 1 lives in d_sub)
   Buf<uint8_t> d_sec{bufs};        // sectioned stream: one large section staged 16-byte aligned, and its output (bytes)
+  shockidx_stream_stats stream_stats = {};  //   how the last call's list was split (shockidx_stream_last_stats)
   hipStream_t s_copy = nullptr;    // slab-pipelined host builds: the H2D stream
   uint8_t *h_rows[2] = {nullptr, nullptr};  // slab-pipelined fd builds: pinned row staging (D2H)
   // download filters over FASTQ: the tile pass keeps each record's line ends (k_fq_tiles<true>)

@@ -112,10 +112,27 @@ hipError_t sidx_filter_read_status(const uint8_t *data, sidx::u64 n, sidx::u64 s
 // the sectioned stream (sidx_stream.hip; control words: sidx_stream.hpp): range check and the sections
 // the segmented path leaves to the single-section filter; a batch's records per section; after the
 // scan of cnt into base, the batch's rows / ordinals / sections and ctl[SS_KEY], ctl[SS_KE]
-hipError_t sidx_stream_classify(const void *d_secs, sidx::u64 nsecs, sidx::u64 n, const int *fmt, sidx::u64 small,
-    sidx::u64 *ctl, sidx::u64 *others, hipStream_t s);
+hipError_t sidx_stream_classify(const void *d_secs, sidx::u64 nsecs, sidx::u64 n, const int *fmt,
+    sidx::u64 small_fastq, sidx::u64 small_fasta, sidx::u64 small_sam, sidx::u64 *ctl, sidx::u64 *others,
+    sidx::u64 *cuts, hipStream_t s);
 hipError_t sidx_stream_count(const uint8_t *data, sidx::u64 n, const void *d_secs, sidx::u64 S, sidx::u64 *cnt,
     hipStream_t s);
+// FASTA / SAM batches: the sections' sequences (boundaries) / lines, the flat rows after the scan, and
+// after the spans ctl[SS_KE], ctl[SS_KEY], ctl[SS_NDELIV]
+hipError_t sidx_stream_fa_count(const uint8_t *data, sidx::u64 n, const void *d_secs, sidx::u64 S, sidx::u64 *cnt,
+    hipStream_t s);
+hipError_t sidx_stream_fa_emit(const uint8_t *data, sidx::u64 n, const void *d_secs, sidx::u64 S, const sidx::u64 *cnt,
+    const sidx::u64 *base, sidx::u64 *rows, sidx::u32 *ord, sidx::u32 *rsec, hipStream_t s);
+hipError_t sidx_stream_sam_count(const uint8_t *data, sidx::u64 n, const void *d_secs, sidx::u64 S, sidx::u64 *cnt,
+    hipStream_t s);
+hipError_t sidx_stream_sam_emit(const uint8_t *data, sidx::u64 n, const void *d_secs, sidx::u64 S, const sidx::u64 *cnt,
+    const sidx::u64 *base, sidx::u64 *rows, sidx::u32 *rsec, hipStream_t s);
+hipError_t sidx_stream_flat_finish(const sidx::u32 *rsec, const sidx::u64 *outlen, sidx::u64 K, int count_nz,
+    sidx::u64 *ctl, hipStream_t s);
+hipError_t sidx_fa_anon_spans_seg(const uint8_t *d, sidx::u64 n, const sidx::u64 *rows, const sidx::u32 *ord,
+    sidx::u64 m, sidx::u64 *bspan, sidx::u64 *outlen, sidx::u64 *firstbad, hipStream_t s);
+hipError_t sidx_fa_anon_write_seg(const uint8_t *d, sidx::u64 n, const sidx::u64 *bspan, const sidx::u64 *outoff,
+    const sidx::u32 *ord, sidx::u64 K, uint8_t *out, hipStream_t s);
 hipError_t sidx_stream_index(const uint8_t *data, sidx::u64 n, const void *d_secs, sidx::u64 S, const sidx::u64 *cnt,
     const sidx::u64 *base, sidx::u64 K, sidx::u64 *rows, sidx::u32 *ord, sidx::u32 *rsec, sidx::u64 *ctl,
     hipStream_t s);

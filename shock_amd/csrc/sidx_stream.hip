@@ -2,8 +2,10 @@
 // Filter (request/streamer.go:78-98) over a list of sections {int64 pos, int64 len} of one node in
 // HBM.  The reference builds a new filter reader per section (s.Filter(sr), streamer.go:86-87), so
 // fastq.Reader.Read (fastq.go:50-132) restarts at every section and a section's end is its reader's
-// end of file.  What is here is the segmented record index over many small sections; spans, scan and
-// writer are the single-section filter's (sidx_filter.hip), on absolute positions of the node.
+// end of file.  What is here is the segmented index over many small sections -- FASTQ records, and
+// under anonymize (which detects the format per section) FASTA sequences and SAM lines, further down;
+// spans, scan and writer are the single-section filter's (sidx_filter.hip), on absolute positions of the
+// node.
 //
 // A section's records are fixed by its '\n' ranks alone.  Read consumes four lines per record and
 // returns at the first record it cannot deliver; a blank first line never starts a record (the
@@ -13,7 +15,8 @@
 // the section's terminal status: nothing or blank lines (io.EOF), a record whose quality line has no
 // '\n' (returned with io.EOF, dropped by the filters), or Read's error.
 //
-//   k_ss_classify  one lane per section: range check; which sections the segmented path cannot take
+//   k_ss_classify  one lane per section: range check; which sections the segmented path cannot take, and
+//                  where a batch (a run of consecutive small sections of one format) starts
 //   k_ss_count     one wave per section: its '\n' count / 4 = the records that have all four line ends
 //   (exclusive scan over the sections, sidx_scan.hpp)
 //   k_ss_emit      one wave per section: the flat row table, each record's ordinal in its section and
@@ -43,11 +46,28 @@ __device__ __forceinline__ bool sec_valid(i64 pos, i64 len, u64 n) {
   return pos >= 0 && len >= 0 && (u64)pos <= n && (u64)len <= n - (u64)pos;
 }
 
+// The small-section limits by format (bytes; 0: that format takes the single-section path).
+struct SmallLimits { u64 fastq, fasta, sam; };
+
+// The format the segmented path takes section i in, 0: it does not (outside the node, too long, or of
+// no detected format).  fmt null: fq2fa, which does not detect and reads everything as FASTQ.
+__device__ __forceinline__ int ss_batched(const i64 *secs, u64 i, u64 n, const int *fmt, const SmallLimits &sm) {
+  const i64 pos = secs[2 * i], len = secs[2 * i + 1];
+  if (!sec_valid(pos, len, n)) return 0;
+  const int f = fmt ? fmt[i] : (int)F_FASTQ;
+  const u64 lim = f == F_FASTQ ? sm.fastq : f == F_FASTA ? sm.fasta : f == F_SAM ? sm.sam : 0;
+  return (u64)len <= lim && lim ? f : 0;
+}
+
 // fmt: the sections' detected formats (anonymize; null for fq2fa, which does not detect,
-// fq2fa.go:18-24).  ctl[SS_INVALID] |= 1 for a section outside the node; a section longer than `small`
-// or not FASTQ is appended to others (any order; the host sorts them), counted in ctl[SS_NOTHER].
-__global__ __launch_bounds__(256) void k_ss_classify(const i64 *secs, u64 nsecs, u64 n, const int *fmt, u64 small,
-                                                     u64 *ctl, u64 *others) {
+// fq2fa.go:18-24).  ctl[SS_INVALID] |= 1 for a section outside the node; a section longer than its
+// format's limit or of no format is appended to others (any order; the host sorts them), counted in
+// ctl[SS_NOTHER].  A batch is a maximal run of consecutive sections the segmented path takes in one
+// format: every section after the first that starts one -- its predecessor is an other or of another
+// format -- is appended to cuts with its format (any order), counted in ctl[SS_NCUT]; section 0's
+// format goes to ctl[SS_FMT0].  A list of small sections of one format reports no other and no cut.
+__global__ __launch_bounds__(256) void k_ss_classify(const i64 *secs, u64 nsecs, u64 n, const int *fmt, SmallLimits sm,
+                                                     u64 *ctl, u64 *others, u64 *cuts) {
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nsecs) return;
   const i64 pos = secs[2 * i], len = secs[2 * i + 1];
@@ -55,9 +75,17 @@ __global__ __launch_bounds__(256) void k_ss_classify(const i64 *secs, u64 nsecs,
     atomicOr((unsigned long long *)&ctl[SS_INVALID], 1ull);
     return;
   }
-  if ((u64)len > small || (fmt && fmt[i] != F_FASTQ)) {
+  const int f = ss_batched(secs, i, n, fmt, sm);
+  if (!f) {
     const u64 k = atomicAdd((unsigned long long *)&ctl[SS_NOTHER], 1ull);
     others[k] = i;  // at most nsecs entries
+    return;
+  }
+  if (i == 0) {
+    ctl[SS_FMT0] = (u64)f;
+  } else if (ss_batched(secs, i - 1, n, fmt, sm) != f) {
+    const u64 k = atomicAdd((unsigned long long *)&ctl[SS_NCUT], 1ull);
+    cuts[k] = (i << SS_CUT_SHIFT) | (u64)f;  // at most nsecs entries
   }
 }
 
@@ -81,7 +109,9 @@ __device__ __forceinline__ u64 ss_wave_max(u64 v) {
   return v;
 }
 
-__global__ __launch_bounds__(256) void k_ss_count(const uint8_t *data, u64 n, const i64 *secs, u64 S, u64 *cnt) {
+// shift 2: FASTQ records (four lines each); shift 0: SAM lines
+__global__ __launch_bounds__(256) void k_ss_count(const uint8_t *data, u64 n, const i64 *secs, u64 S, u64 *cnt,
+                                                  u32 shift) {
   const int lane = threadIdx.x & 63;
   const u64 nw = (u64)gridDim.x * (blockDim.x / 64);
   for (u64 i = (u64)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); i < S; i += nw) {
@@ -93,7 +123,7 @@ __global__ __launch_bounds__(256) void k_ss_count(const uint8_t *data, u64 n, co
     }
     u64 t = c;
     for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-    if (lane == 0) cnt[i] = t >> 2;
+    if (lane == 0) cnt[i] = t >> shift;
   }
 }
 
@@ -189,21 +219,226 @@ __global__ void k_ss_finish(const u64 *base, u64 K, u64 *ctl) {
   ctl[SS_KE] = key == ~0ull ? K : base[key >> SS_SEC_SHIFT] + ((key >> 4) & SS_REC_MASK);
 }
 
+// ---- FASTA and SAM sections (anonymize) --------------------------------------------------------------
+// fasta.Reader.Read's sequences in a section are cut at the section's FASTA boundaries: a '>' at p whose
+// last '\n' in [pos, p) lies after the last '>' in [pos, p) (fasta.go:100-138, over the section's bytes
+// alone: its first '>' is never a boundary, whatever precedes it in the node).  Sequence k is the read
+// [start_k, B_k), start_0 = pos, start_k = B_{k-1}; the read that runs to the section end comes back with
+// io.EOF and is dropped (fasta.go:86-88), so a section has no terminal status and the first failing
+// sequence in flat order is the first failure of the stream.  sam.Reader.Read's items are the section's
+// '\n'-terminated lines; a last piece without '\n' is io.EOF and delivers nothing (sam.go:49,72-74).
+//
+//   k_ss_fa_count  one wave per section: its boundaries
+//   k_ss_fa_emit   the flat row table (start, B_k), each sequence's ordinal in its section and its section
+//   k_ss_count     (shift 0) a section's '\n'
+//   k_ss_sam_emit  the flat row table (offset, length) of the lines, and each line's section
+//   k_ss_flat_finish  the first failing flat item -> its section, the items before it, the lines delivered
+// Spans and writers are sidx_filter.hip's, over the flat rows.
+
+// ss_nl_mask for the two byte classes of the boundary rule
+__device__ __forceinline__ void ss_nl_gt_masks(const uint8_t *data, u64 n, u64 b0, int lane, u64 pos, u64 end, u64 &a,
+                                               u32 &mnl, u32 &mgt) {
+  a = b0 + 16ull * lane;
+  mnl = mgt = 0;
+  if (a >= end) return;
+  const uint4 v = (a + 16 <= n) ? load16(data + a) : load16_partial(data, a, n);
+  u32 keep = 0xFFFFu;
+  if (a < pos) keep &= ~0u << (u32)(pos - a);
+  if (end - a < 16) keep &= (1u << (u32)(end - a)) - 1u;
+  mnl = eq16(v, '\n') & keep;
+  mgt = eq16(v, '>') & keep;
+}
+
+// the last set byte of a lane's mask in its 1 KiB step, position in the step + 1 (0: none)
+__device__ __forceinline__ u32 ss_last_in_step(u32 m, int lane) {
+  return m ? 16u * (u32)lane + 32u - (u32)__builtin_clz(m) : 0u;
+}
+// the wave's exclusive maximum of v (0 in lane 0) and its maximum over all lanes
+__device__ __forceinline__ u32 ss_excl_max(u32 v, int lane, u32 &all) {
+  const u32 inc = wave_scan_max(v);
+  all = (u32)__shfl((int)inc, 63, 64);
+  const u32 p = (u32)__shfl_up((int)inc, 1, 64);
+  return lane ? p : 0u;
+}
+
+// The boundary '>' bits of the lane's 16 bytes at a (bnd_bits of sidx_filter.hip for a 16-bit word);
+// cnl / cgt: the section's last '\n' / '>' before this 1 KiB step (position + 1, 0: none), carried on
+// to the next step.
+__device__ __forceinline__ u32 ss_fa_bnd(u32 mnl, u32 mgt, u64 a, u64 b0, int lane, u64 &cnl, u64 &cgt) {
+  u32 tnl, tgt;
+  const u32 pnl = ss_excl_max(ss_last_in_step(mnl, lane), lane, tnl);
+  const u32 pgt = ss_excl_max(ss_last_in_step(mgt, lane), lane, tgt);
+  const u64 lnl = pnl ? b0 + pnl : cnl, lgt = pgt ? b0 + pgt : cgt;  // before the lane's bytes
+  u32 out = 0;
+  for (u32 m = mgt; m; m &= m - 1) {
+    const u32 i = (u32)__builtin_ctz(m), below = (1u << i) - 1u;
+    const u64 ln = (mnl & below) ? a + 32 - (u64)__builtin_clz(mnl & below) : lnl;
+    const u64 lg = (mgt & below) ? a + 32 - (u64)__builtin_clz(mgt & below) : lgt;
+    if (ln > lg) out |= 1u << i;
+  }
+  if (tnl) cnl = b0 + tnl;
+  if (tgt) cgt = b0 + tgt;
+  return out;
+}
+
+__global__ __launch_bounds__(256) void k_ss_fa_count(const uint8_t *data, u64 n, const i64 *secs, u64 S, u64 *cnt) {
+  const int lane = threadIdx.x & 63;
+  const u64 nw = (u64)gridDim.x * (blockDim.x / 64);
+  for (u64 i = (u64)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); i < S; i += nw) {
+    const u64 pos = (u64)secs[2 * i], end = pos + (u64)secs[2 * i + 1];
+    u64 cnl = 0, cgt = 0;
+    u32 c = 0;
+    for (u64 b0 = pos & ~15ull; b0 < end; b0 += 1024) {
+      u64 a;
+      u32 mnl, mgt;
+      ss_nl_gt_masks(data, n, b0, lane, pos, end, a, mnl, mgt);
+      c += (u32)__builtin_popcount(ss_fa_bnd(mnl, mgt, a, b0, lane, cnl, cgt));
+    }
+    u64 t = c;
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+    if (lane == 0) cnt[i] = t;
+  }
+}
+
+// rows[2 r] = sequence r's start, rows[2 r + 1] = its boundary B_k (the read's end); ord[r] = its ordinal
+// within its section, rsec[r] = its section (relative to the batch).  Like k_ss_emit, an end goes to
+// slot q and the next start to slot q + 1.
+__global__ __launch_bounds__(256) void k_ss_fa_emit(const uint8_t *data, u64 n, const i64 *secs, u64 S, const u64 *cnt,
+                                                    const u64 *base, u64 *rows, u32 *ord, u32 *rsec) {
+  const int lane = threadIdx.x & 63;
+  const u64 nw = (u64)gridDim.x * (blockDim.x / 64);
+  for (u64 i = (u64)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); i < S; i += nw) {
+    const u64 nb = cnt[i], r0 = base[i];
+    if (!nb) continue;
+    const u64 pos = (u64)secs[2 * i], end = pos + (u64)secs[2 * i + 1];
+    if (lane == 0) rows[2 * r0] = pos;
+    u64 cnl = 0, cgt = 0, rank0 = 0;  // boundaries before this step
+    for (u64 b0 = pos & ~15ull; b0 < end && rank0 < nb; b0 += 1024) {
+      u64 a;
+      u32 mnl, mgt;
+      ss_nl_gt_masks(data, n, b0, lane, pos, end, a, mnl, mgt);
+      u32 m = ss_fa_bnd(mnl, mgt, a, b0, lane, cnl, cgt);
+      const u32 c = (u32)__builtin_popcount(m);
+      const u32 incl = wave_scan_add(c);
+      u64 q = rank0 + incl - c;
+      for (; m && q < nb; m &= m - 1, ++q) {
+        const u64 b = a + (u64)__builtin_ctz(m);
+        rows[2 * (r0 + q) + 1] = b;
+        ord[r0 + q] = (u32)q;
+        rsec[r0 + q] = (u32)i;
+        if (q + 1 < nb) rows[2 * (r0 + q + 1)] = b;
+      }
+      rank0 += (u32)__shfl((int)incl, 63, 64);
+    }
+  }
+}
+
+// rows[2 r] = line r's offset, rows[2 r + 1] = its length with the '\n' (the rows of the line index);
+// rsec[r] = its section (relative to the batch).  cnt: the sections' '\n' counts.
+__global__ __launch_bounds__(256) void k_ss_sam_emit(const uint8_t *data, u64 n, const i64 *secs, u64 S, const u64 *cnt,
+                                                     const u64 *base, u64 *rows, u32 *rsec) {
+  const int lane = threadIdx.x & 63;
+  const u64 nw = (u64)gridDim.x * (blockDim.x / 64);
+  for (u64 i = (u64)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); i < S; i += nw) {
+    const u64 nl = cnt[i], r0 = base[i];
+    if (!nl) continue;
+    const u64 pos = (u64)secs[2 * i], end = pos + (u64)secs[2 * i + 1];
+    u64 start = pos, rank0 = 0;  // where the line open at the step's start begins; '\n' before this step
+    for (u64 b0 = pos & ~15ull; b0 < end && rank0 < nl; b0 += 1024) {
+      u64 a;
+      u32 m = ss_nl_mask(data, n, b0, lane, pos, end, a);
+      const u32 mnl = m;
+      u32 tnl;
+      const u32 pnl = ss_excl_max(ss_last_in_step(mnl, lane), lane, tnl);
+      const u64 lstart = pnl ? b0 + pnl : start;  // the line open at the lane's first byte
+      const u32 c = (u32)__builtin_popcount(m);
+      const u32 incl = wave_scan_add(c);
+      u64 q = rank0 + incl - c;
+      for (; m && q < nl; m &= m - 1, ++q) {
+        const u32 k = (u32)__builtin_ctz(m), below = (1u << k) - 1u;
+        const u64 s = (mnl & below) ? a + 32 - (u64)__builtin_clz(mnl & below) : lstart;
+        rows[2 * (r0 + q)] = s;
+        rows[2 * (r0 + q) + 1] = a + k + 1 - s;
+        rsec[r0 + q] = (u32)i;
+      }
+      if (tnl) start = b0 + tnl;
+      rank0 += (u32)__shfl((int)incl, 63, 64);
+    }
+  }
+}
+
+// After the spans kernel of a FASTA or SAM batch: ctl[SS_BAD] is the first failing flat item (~0: none).
+// ctl[SS_KE] = the items before it, ctl[SS_KEY] = its section within the batch (~0: none) and, count_nz
+// (SAM: blank and '@' lines deliver nothing), ctl[SS_NDELIV] += the items before it with an output
+// (zeroed by the caller).
+__global__ __launch_bounds__(256) void k_ss_flat_finish(const u32 *rsec, const u64 *outlen, u64 K, int count_nz, u64 *ctl) {
+  const u64 bad = ctl[SS_BAD];
+  const u64 Ke = bad < K ? bad : K;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    ctl[SS_KE] = Ke;
+    ctl[SS_KEY] = bad < K ? (u64)rsec[bad] : ~0ull;
+  }
+  if (!count_nz) return;
+  u32 c = 0;
+  for (u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x; k < Ke; k += (u64)gridDim.x * blockDim.x) c += outlen[k] != 0;
+  u64 t = c;
+  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+  if ((threadIdx.x & 63) == 0 && t) atomicAdd((unsigned long long *)&ctl[SS_NDELIV], (unsigned long long)t);
+}
+
 }  // namespace sidx
 
 using namespace sidx;
 
 static u32 ss_wave_grid(u64 S) { return (u32)((S + 3) / 4 < 262144 ? (S + 3) / 4 : 262144); }
 
-extern "C" hipError_t sidx_stream_classify(const void *d_secs, u64 nsecs, u64 n, const int *fmt, u64 small, u64 *ctl,
-                                           u64 *others, hipStream_t s) {
+// small_*: the small-section limit of each format; others / cuts: nsecs words each; ctl zeroed
+extern "C" hipError_t sidx_stream_classify(const void *d_secs, u64 nsecs, u64 n, const int *fmt, u64 small_fastq,
+                                           u64 small_fasta, u64 small_sam, u64 *ctl, u64 *others, u64 *cuts,
+                                           hipStream_t s) {
   if (nsecs) hipLaunchKernelGGL(k_ss_classify, dim3((u32)((nsecs + 255) / 256)), dim3(256), 0, s, (const i64 *)d_secs,
-                                nsecs, n, fmt, small, ctl, others);
+                                nsecs, n, fmt, SmallLimits{small_fastq, small_fasta, small_sam}, ctl, others, cuts);
   return hipGetLastError();
 }
 
 extern "C" hipError_t sidx_stream_count(const uint8_t *data, u64 n, const void *d_secs, u64 S, u64 *cnt, hipStream_t s) {
-  if (S) hipLaunchKernelGGL(k_ss_count, dim3(ss_wave_grid(S)), dim3(256), 0, s, data, n, (const i64 *)d_secs, S, cnt);
+  if (S) hipLaunchKernelGGL(k_ss_count, dim3(ss_wave_grid(S)), dim3(256), 0, s, data, n, (const i64 *)d_secs, S, cnt, 2u);
+  return hipGetLastError();
+}
+
+// FASTA: cnt[i] = section i's boundaries (the sequences Read delivers before the one that ends at the
+// section end)
+extern "C" hipError_t sidx_stream_fa_count(const uint8_t *data, u64 n, const void *d_secs, u64 S, u64 *cnt,
+                                           hipStream_t s) {
+  if (S) hipLaunchKernelGGL(k_ss_fa_count, dim3(ss_wave_grid(S)), dim3(256), 0, s, data, n, (const i64 *)d_secs, S, cnt);
+  return hipGetLastError();
+}
+// after the scan of cnt into base: rows (2 K words) / ord / rsec (K words) of the K sequences
+extern "C" hipError_t sidx_stream_fa_emit(const uint8_t *data, u64 n, const void *d_secs, u64 S, const u64 *cnt,
+                                          const u64 *base, u64 *rows, u32 *ord, u32 *rsec, hipStream_t s) {
+  if (S) hipLaunchKernelGGL(k_ss_fa_emit, dim3(ss_wave_grid(S)), dim3(256), 0, s, data, n, (const i64 *)d_secs, S, cnt,
+                            base, rows, ord, rsec);
+  return hipGetLastError();
+}
+// SAM: cnt[i] = section i's '\n'-terminated lines; rows (2 K words) / rsec (K words) of the K lines
+extern "C" hipError_t sidx_stream_sam_count(const uint8_t *data, u64 n, const void *d_secs, u64 S, u64 *cnt,
+                                            hipStream_t s) {
+  if (S) hipLaunchKernelGGL(k_ss_count, dim3(ss_wave_grid(S)), dim3(256), 0, s, data, n, (const i64 *)d_secs, S, cnt, 0u);
+  return hipGetLastError();
+}
+extern "C" hipError_t sidx_stream_sam_emit(const uint8_t *data, u64 n, const void *d_secs, u64 S, const u64 *cnt,
+                                           const u64 *base, u64 *rows, u32 *rsec, hipStream_t s) {
+  if (S) hipLaunchKernelGGL(k_ss_sam_emit, dim3(ss_wave_grid(S)), dim3(256), 0, s, data, n, (const i64 *)d_secs, S, cnt,
+                            base, rows, rsec);
+  return hipGetLastError();
+}
+// after the spans of the K flat items (first failure in ctl[SS_BAD]): ctl[SS_KE], ctl[SS_KEY] and, count_nz,
+// ctl[SS_NDELIV] (zeroed by the caller)
+extern "C" hipError_t sidx_stream_flat_finish(const u32 *rsec, const u64 *outlen, u64 K, int count_nz, u64 *ctl,
+                                              hipStream_t s) {
+  const u64 nb = (K + 255) / 256;
+  hipLaunchKernelGGL(k_ss_flat_finish, dim3((u32)(nb < 1 ? 1 : nb < 4096 ? nb : 4096)), dim3(256), 0, s, rsec, outlen, K,
+                     count_nz, ctl);
   return hipGetLastError();
 }
 
