@@ -49,7 +49,8 @@ extern "C" {
  *    end invariants (SHOCKIDX_EINTERNAL instead of a short table).
  *    Added since without a version change (purely additive): shockidx_column_device,
  *    shockidx_column_fd, shockidx_stream_filter_device, shockidx_download_plan,
- *    shockidx_stream_last_stats */
+ *    shockidx_stream_last_stats, shockidx_build_batch_device, shockidx_build_batch_host,
+ *    shockidx_batch_error, shockidx_batch_last_stats */
 #define SHOCKIDX_ABI_VERSION 5
 
 /* index kinds = the registry keys served (index/index.go:21-28) */
@@ -493,6 +494,68 @@ int shockidx_column_device(shockidx_ctx *ctx, const void *d_data, uint64_t n, in
  * *rows receives a malloc'ed table of result->count rows (free with shockidx_free). */
 int shockidx_column_fd(shockidx_ctx *ctx, int fd, uint64_t n, int column, uint64_t **rows,
                        shockidx_result *result);
+
+/* ---- The batch build: many small nodes indexed in one call -----------------------------------
+ * A batch is a list of nnodes nodes {int64 pos, int64 len} (the layout of the stream's sections) of
+ * one byte arena, both in HBM, with one kind and one fmt (AUTO: detected per node) for all of them.
+ * Node i's result is exactly shockidx_build_device's over the bytes [pos, pos + len) alone: count,
+ * format, status, Go's error text and the rows, whose offsets are relative to the node's first byte.
+ * Nodes are independent: a node in error, or of no detectable format, changes nothing for the
+ * others, and no byte outside a node influences its result.  pos must be 16-byte aligned and
+ * pos + len <= data_len; anything else is SHOCKIDX_EINVAL for the call with nothing written.
+ * d_data and d_rows are 16-byte aligned, d_nodes 8-byte aligned.
+ *
+ * Rows of node i are d_rows[row_off .. row_off + count); row_off does not decrease along the list
+ * and the regions do not overlap (the table is not dense behind a node that ended in an error).
+ * *rows_total is the table's extent in rows.  A row_cap below it returns SHOCKIDX_ESPACE with
+ * *rows_total = a capacity with which the same call succeeds, and nothing written to d_rows.
+ *
+ * The call's return code and result->status report system errors only; a format error is per node,
+ * in items[i].status, and the call returns SHOCKIDX_OK.  result->count = the nodes with status OK.
+ * Nodes of at most SHOCKIDX_BATCH_SMALL bytes (environment, read per call; default 256 KiB; 0: none)
+ * are indexed together, in a number of kernel launches and host waits that does not depend on
+ * nnodes, on which formats occur or on how they interleave; longer ones go through the single build
+ * one at a time, in list order, into their region of the same table (one wave still counts such a
+ * node's rows first: a node of hundreds of MiB belongs in shockidx_build_device). */
+typedef struct shockidx_batch_item { /* one per node, host memory */
+  uint64_t count;     /* rows valid for this node: the records before an error */
+  uint64_t row_off;   /* its first row in the batch's table (rows, not bytes) */
+  int32_t format;     /* SHOCKIDX_FMT_* indexed (SHOCKIDX_FMT_NONE: none detected) */
+  int32_t status;     /* SHOCKIDX_OK or SHOCKIDX_EFORMAT */
+  uint32_t term_code; /* device status of the terminating record (diagnostic) */
+  uint32_t path;      /* 5: the batched walk; otherwise the single build's path (1, 2) */
+  uint64_t err_pos;   /* FASTA: the invalid piece, relative to the node */
+  uint64_t err_len;
+} shockidx_batch_item;
+int shockidx_build_batch_device(shockidx_ctx *ctx, const void *d_data, uint64_t data_len, const void *d_nodes,
+                                uint64_t nnodes, int kind, int fmt, void *d_rows, uint64_t row_cap,
+                                shockidx_batch_item *items, uint64_t *rows_total, shockidx_result *result);
+/* The same over nnodes bodies in host memory: packed into one arena at 16-byte aligned positions
+ * (in list order), copied to HBM and indexed.  *rows receives one malloc'ed table (free with
+ * shockidx_free); items[i].row_off places node i in it.  The context keeps the packed arena until
+ * its next call, for shockidx_batch_error(ctx, NULL, ...). */
+int shockidx_build_batch_host(shockidx_ctx *ctx, const void *const *bodies, const uint64_t *lens, uint64_t nnodes,
+                              int kind, int fmt, uint64_t **rows, shockidx_batch_item *items,
+                              shockidx_result *result);
+/* Go's error text for one failed node of the last batch, byte for byte what the single build
+ * reports (at most 255 bytes; *len = the bytes written to buf, never more than cap; no NUL is
+ * added).  d_data: the arena of the device call, or NULL after shockidx_build_batch_host; node: the
+ * node's {int64 pos, int64 len} in host memory (after _host its position in the packed arena:
+ * node 0 at 0, each next node at the 16-byte boundary at or after its predecessor's end).  A node
+ * whose status is SHOCKIDX_OK has an empty text. */
+int shockidx_batch_error(shockidx_ctx *ctx, const void *d_data, const shockidx_batch_item *item, const void *node,
+                         char *buf, uint64_t cap, uint64_t *len);
+/* How the context's last batch call ran (the results do not depend on it). */
+typedef struct shockidx_batch_stats {
+  uint64_t nodes;        /* nnodes of the call */
+  uint64_t batches;      /* batched walks (0 or 1: every small node, whatever its format) */
+  uint64_t batched;      /* nodes inside it */
+  uint64_t singles;      /* nodes that went through the single build */
+  uint64_t by_format[4]; /* nodes indexed as FASTQ, FASTA, SAM, line */
+  uint64_t launches;     /* kernel launches the batched walk made (a single counts as one) */
+  uint64_t waits;        /* host waits on the stream (a single adds its build's own) */
+} shockidx_batch_stats;
+int shockidx_batch_last_stats(const shockidx_ctx *ctx, shockidx_batch_stats *out);
 
 void shockidx_free(void *p);
 const char *shockidx_strerror(int code);

@@ -35,6 +35,7 @@ EXPORTS = ("shockidx_ctx_create", "shockidx_ctx_destroy", "shockidx_build_device
            "shockidx_chunkrecord_device", "shockidx_chunkrecord_fd", "shockidx_chunkrecord_subset_device", "shockidx_create_subset_index",
            "shockidx_column_device", "shockidx_column_fd",
            "shockidx_idx_part", "shockidx_idx_range", "shockidx_filter_device", "shockidx_stream_filter_device", "shockidx_stream_last_stats",
+           "shockidx_build_batch_device", "shockidx_build_batch_host", "shockidx_batch_error", "shockidx_batch_last_stats",
            "shockidx_download_plan", "shockidx_ctx_trim",
            "shockidx_ctx_workspace_bytes", "shockidx_ctx_set_dev_cap", "shockidx_multi_create", "shockidx_multi_destroy", "shockidx_multi_rccl",
            "shockidx_multi_build_host", "shockidx_multi_build_fd", "shockidx_multi_create_index", "shockidx_multi_plan",
@@ -99,6 +100,21 @@ class StreamStats(ctypes.Structure):
                 ("singles", ctypes.c_uint64), ("by_format", ctypes.c_uint64 * 3)]
 
 
+class BatchItem(ctypes.Structure):
+    """mirrors shockidx_batch_item (include/shockidx.h)"""
+    _fields_ = [("count", ctypes.c_uint64), ("row_off", ctypes.c_uint64), ("format", ctypes.c_int32),
+                ("status", ctypes.c_int32), ("term_code", ctypes.c_uint32), ("path", ctypes.c_uint32),
+                ("err_pos", ctypes.c_uint64), ("err_len", ctypes.c_uint64)]
+
+
+class BatchStats(ctypes.Structure):
+    """mirrors shockidx_batch_stats (include/shockidx.h)"""
+    _fields_ = [("nodes", ctypes.c_uint64), ("batches", ctypes.c_uint64), ("batched", ctypes.c_uint64),
+                ("singles", ctypes.c_uint64), ("by_format", ctypes.c_uint64 * 4), ("launches", ctypes.c_uint64),
+                ("waits", ctypes.c_uint64)]
+
+
+assert ctypes.sizeof(BatchItem) == 48
 assert ctypes.sizeof(SlabSummary) == 64
 assert ctypes.sizeof(Slab) == 56
 
@@ -212,6 +228,17 @@ def lib():
     L.shockidx_stream_filter_device.restype = i32
     L.shockidx_stream_last_stats.argtypes = [vp, ctypes.POINTER(StreamStats)]
     L.shockidx_stream_last_stats.restype = i32
+    PItem = ctypes.POINTER(BatchItem)
+    L.shockidx_build_batch_device.argtypes = [vp, vp, u64, vp, u64, i32, i32, vp, u64, PItem,
+                                              ctypes.POINTER(ctypes.c_uint64), PRes]
+    L.shockidx_build_batch_device.restype = i32
+    L.shockidx_build_batch_host.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_uint64), u64, i32, i32,
+                                            PPu64, PItem, PRes]
+    L.shockidx_build_batch_host.restype = i32
+    L.shockidx_batch_error.argtypes = [vp, vp, PItem, vp, ctypes.c_char_p, u64, ctypes.POINTER(ctypes.c_uint64)]
+    L.shockidx_batch_error.restype = i32
+    L.shockidx_batch_last_stats.argtypes = [vp, ctypes.POINTER(BatchStats)]
+    L.shockidx_batch_last_stats.restype = i32
     L.shockidx_download_plan.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), u64, vp, u64, ctypes.c_int64,
                                          vp, u64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp, u64,
                                          ctypes.POINTER(ctypes.c_int64), PSub]

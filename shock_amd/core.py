@@ -26,6 +26,23 @@ class IndexResult:
     flags: int = 0
     fixups: int = 0
     fix_tiles: int = 0
+    row_off: int = 0  # batch builds: the node's first row in the batch's table
+
+    @property
+    def ok(self) -> bool:
+        return self.status == L.OK
+
+
+@dataclass
+class BatchResult:
+    """One batch build: the call's status (system errors only), the nodes with status OK, the table's
+    extent in rows (with ESPACE: a capacity with which the call succeeds) and one IndexResult per node."""
+    status: int
+    count: int
+    rows_total: int
+    items: list
+    err: bytes | None = None
+    timings: dict = field(default_factory=dict)
 
     @property
     def ok(self) -> bool:
@@ -154,6 +171,87 @@ class Context:
                      stream: int | None = None) -> IndexResult:
         """Device-resident build over DeviceBuffers (rows capacity = rows.nbytes // 16)."""
         return self.build_device(data.ptr, n, rows.ptr, rows.nbytes // 16, kind, fmt, stream)
+
+    # -- batch build: many small nodes in one device call -----------------------------------
+    def _batch_items(self, items, nnodes, d_data, nodes, table=None):
+        """shockidx_batch_item[] -> IndexResults; err through shockidx_batch_error for failed nodes only
+        (nodes: int64 [nnodes, 2] {pos, len} on the host; d_data None: the context's packed arena)."""
+        out = []
+        buf = ctypes.create_string_buffer(256)
+        for i in range(nnodes):
+            it = items[i]
+            err = None
+            if it.status != L.OK:
+                n = ctypes.c_uint64(0)
+                rc = self._lib.shockidx_batch_error(self._h, d_data, ctypes.byref(it), nodes[i].ctypes.data, buf, 255,
+                                                    ctypes.byref(n))
+                if rc != L.OK:
+                    raise L.ShockIdxError(rc, "shockidx_batch_error")
+                err = buf.raw[:n.value]
+            rows = None
+            if table is not None:
+                rows = table[int(it.row_off):int(it.row_off) + int(it.count)]
+            out.append(IndexResult(count=int(it.count), fmt=L.FMT_NAMES.get(it.format), status=int(it.status), err=err,
+                                   rows=rows, path=int(it.path), term_code=int(it.term_code), row_off=int(it.row_off)))
+        return out
+
+    def build_batch_device(self, d_data: int, data_len: int, d_nodes: int, nnodes: int, d_rows: int, row_cap: int,
+                           kind="record", fmt=None) -> BatchResult:
+        """nnodes nodes {int64 pos, int64 len} (d_nodes) of the arena d_data, both in HBM, indexed in one
+        call: items[i] is what build_device gives over node i's bytes alone, its rows at
+        d_rows[row_off .. row_off + count).  A short row_cap returns ESPACE with rows_total = the
+        capacity needed and nothing written; a bad list returns EINVAL."""
+        res = L.Result()
+        items = (L.BatchItem * max(nnodes, 1))()
+        total = ctypes.c_uint64(0)
+        rc = self._lib.shockidx_build_batch_device(self._h, d_data, data_len, d_nodes, nnodes, _kind(kind), _fmt(fmt),
+                                                   d_rows, row_cap, items, ctypes.byref(total), ctypes.byref(res))
+        r = _result(res, rc)
+        out = []
+        if rc == L.OK and nnodes:
+            nodes = np.zeros((nnodes, 2), dtype=np.int64)
+            rc2 = self._lib.shockidx_memcpy_d2h(self._h, nodes.ctypes.data, d_nodes, nodes.nbytes)
+            if rc2 != L.OK:
+                raise L.ShockIdxError(rc2, "shockidx_memcpy_d2h")
+            out = self._batch_items(items, nnodes, d_data, nodes)
+        return BatchResult(status=rc, count=r.count, rows_total=int(total.value), items=out, err=r.err,
+                           timings=r.timings)
+
+    def build_batch_host(self, bodies, kind="record", fmt=None) -> list:
+        """One IndexResult per body (bytes-like), each with its own rows view, count, format and status,
+        from one device call over all of them (shockidx_build_batch_host)."""
+        bufs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in bodies]
+        K = len(bufs)
+        ptrs = (ctypes.c_void_p * max(K, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (ctypes.c_uint64 * max(K, 1))(*[b.size for b in bufs])
+        items = (L.BatchItem * max(K, 1))()
+        res = L.Result()
+        rows_p = ctypes.POINTER(ctypes.c_uint64)()
+        rc = self._lib.shockidx_build_batch_host(self._h, ptrs, lens, K, _kind(kind), _fmt(fmt), ctypes.byref(rows_p),
+                                                 items, ctypes.byref(res))
+        if rc != L.OK:
+            if rows_p:
+                self._lib.shockidx_free(ctypes.cast(rows_p, ctypes.c_void_p))
+            raise L.ShockIdxError(rc, bytes(res.err)[:res.err_len].decode("utf-8", "replace"))
+        total = max([int(items[i].row_off) + int(items[i].count) for i in range(K)], default=0)
+        table = _take_rows(rows_p, total)
+        nodes = np.zeros((max(K, 1), 2), dtype=np.int64)
+        pos = 0
+        for i, b in enumerate(bufs):  # the packed arena: each body at the next 16-byte boundary
+            nodes[i] = (pos, b.size)
+            pos = (pos + b.size + 15) & ~15
+        return self._batch_items(items, K, None, nodes, table)
+
+    def batch_stats(self) -> dict:
+        """How the last batch call ran (shockidx_batch_last_stats): nodes, batches, batched, singles,
+        by_format (nodes indexed as FASTQ, FASTA, SAM, line), and the kernel launches and host waits it made."""
+        st = L.BatchStats()
+        rc = self._lib.shockidx_batch_last_stats(self._h, ctypes.byref(st))
+        if rc != L.OK:
+            raise L.ShockIdxError(rc, "shockidx_batch_last_stats")
+        return {"nodes": int(st.nodes), "batches": int(st.batches), "batched": int(st.batched),
+                "singles": int(st.singles), "by_format": [int(v) for v in st.by_format],
+                "launches": int(st.launches), "waits": int(st.waits)}
 
     def chunkrecord_device(self, d_data: int, n: int, d_rows: int, row_cap: int, fmt=None, chunk: int = 0) -> IndexResult:
         """chunkRecord.Create (index/chunkrecord.go:41-99) over device memory; chunk 0 = 1 MiB."""

@@ -197,7 +197,7 @@ const char *status_message(uint32_t code) {
   }
 }
 
-static std::mutex &device_mutex(int device) {
+std::mutex &device_mutex(int device) {
   static std::mutex mu[64];
   return mu[device & 63];
 }

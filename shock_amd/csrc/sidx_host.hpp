@@ -125,6 +125,9 @@ struct shockidx_ctx {
   Buf<uint8_t> d_plan{bufs};       // download plan: the level-2 workspace of CHUNK_RANGE (level 1 lives in d_sub)
   Buf<uint8_t> d_sec{bufs};        // sectioned stream: one large section staged 16-byte aligned, and its output (bytes)
   shockidx_stream_stats stream_stats = {};  //   how the last call's list was split (shockidx_stream_last_stats)
+  Buf<uint8_t> d_batch{bufs};      // batch build: per-node formats, counts, first rows, slots, items, singles (bytes)
+  Buf<uint8_t> d_bnodes{bufs};     //   the host entry point's node list (bytes)
+  shockidx_batch_stats batch_stats = {};  //   how the last batch call ran (shockidx_batch_last_stats)
   hipStream_t s_copy = nullptr;    // slab-pipelined host builds: the H2D stream
   uint8_t *h_rows[2] = {nullptr, nullptr};  // slab-pipelined fd builds: pinned row staging (D2H)
   // download filters over FASTQ: the tile pass keeps each record's line ends (k_fq_tiles<true>)
@@ -231,6 +234,8 @@ int respeculate(shockidx_ctx *c, const sidx::DevResult &dr, int *kfmt, shockidx_
 int run_index(shockidx_ctx *c, const uint8_t *d_data, sidx::u64 n, int kfmt, sidx::u64 *d_rows, sidx::u64 row_cap,
               hipStream_t s, sidx::DevResult *dr, shockidx_result *res, const SlabGeom *geom = nullptr,
               bool general = false, const int *gate = nullptr);
+// one build's device work at a time per GPU: held around the kernels of a build (run_index takes it itself)
+std::mutex &device_mutex(int device);
 // SHOCKIDX_VERIFY is set (and not "0"): builds check their finished table on the device
 bool verify_rows();
 int translate(shockidx_ctx *c, const sidx::DevResult &dr, const uint8_t *d_data, hipStream_t s, shockidx_result *res);

@@ -8,6 +8,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "sidx_batch.hpp"
 #include "sidx_common.hpp"
 
 extern "C" {
@@ -136,6 +137,12 @@ hipError_t sidx_fa_anon_write_seg(const uint8_t *d, sidx::u64 n, const sidx::u64
 hipError_t sidx_stream_index(const uint8_t *data, sidx::u64 n, const void *d_secs, sidx::u64 S, const sidx::u64 *cnt,
     const sidx::u64 *base, sidx::u64 K, sidx::u64 *rows, sidx::u32 *ord, sidx::u32 *rsec, sidx::u64 *ctl,
     hipStream_t s);
+// the batch build (sidx_batch.hip; arguments and control words: sidx_batch.hpp): the range check and
+// the singles (ctl zeroed by the caller); nat[i] of every node; after the scan of nat into base the
+// layout, rows, checks and items (total_bound: row_cap; *launches += the kernels launched)
+hipError_t sidx_batch_classify(const sidx::BatchArgs *p, hipStream_t s);
+hipError_t sidx_batch_count(const sidx::BatchArgs *p, hipStream_t s);
+hipError_t sidx_batch_index(const sidx::BatchArgs *p, sidx::u64 total_bound, sidx::u32 *launches, hipStream_t s);
 hipError_t sidx_range_flags(const sidx::u64 *rows, sidx::u64 nrows, sidx::u64 a0, sidx::u64 nr, sidx::u32 *flags,
     hipStream_t s);
 hipError_t sidx_range_emit(const sidx::u64 *rows, sidx::u64 nrows, sidx::u64 a0, sidx::u64 nr,

@@ -38,6 +38,7 @@
 #include "sidx_device.hpp"
 #include "sidx_fastq_read.hpp"
 #include "sidx_launch.hpp"
+#include "sidx_seg.hpp"
 #include "sidx_stream.hpp"
 
 namespace sidx {
@@ -247,38 +248,6 @@ __device__ __forceinline__ void ss_nl_gt_masks(const uint8_t *data, u64 n, u64 b
   if (end - a < 16) keep &= (1u << (u32)(end - a)) - 1u;
   mnl = eq16(v, '\n') & keep;
   mgt = eq16(v, '>') & keep;
-}
-
-// the last set byte of a lane's mask in its 1 KiB step, position in the step + 1 (0: none)
-__device__ __forceinline__ u32 ss_last_in_step(u32 m, int lane) {
-  return m ? 16u * (u32)lane + 32u - (u32)__builtin_clz(m) : 0u;
-}
-// the wave's exclusive maximum of v (0 in lane 0) and its maximum over all lanes
-__device__ __forceinline__ u32 ss_excl_max(u32 v, int lane, u32 &all) {
-  const u32 inc = wave_scan_max(v);
-  all = (u32)__shfl((int)inc, 63, 64);
-  const u32 p = (u32)__shfl_up((int)inc, 1, 64);
-  return lane ? p : 0u;
-}
-
-// The boundary '>' bits of the lane's 16 bytes at a (bnd_bits of sidx_filter.hip for a 16-bit word);
-// cnl / cgt: the section's last '\n' / '>' before this 1 KiB step (position + 1, 0: none), carried on
-// to the next step.
-__device__ __forceinline__ u32 ss_fa_bnd(u32 mnl, u32 mgt, u64 a, u64 b0, int lane, u64 &cnl, u64 &cgt) {
-  u32 tnl, tgt;
-  const u32 pnl = ss_excl_max(ss_last_in_step(mnl, lane), lane, tnl);
-  const u32 pgt = ss_excl_max(ss_last_in_step(mgt, lane), lane, tgt);
-  const u64 lnl = pnl ? b0 + pnl : cnl, lgt = pgt ? b0 + pgt : cgt;  // before the lane's bytes
-  u32 out = 0;
-  for (u32 m = mgt; m; m &= m - 1) {
-    const u32 i = (u32)__builtin_ctz(m), below = (1u << i) - 1u;
-    const u64 ln = (mnl & below) ? a + 32 - (u64)__builtin_clz(mnl & below) : lnl;
-    const u64 lg = (mgt & below) ? a + 32 - (u64)__builtin_clz(mgt & below) : lgt;
-    if (ln > lg) out |= 1u << i;
-  }
-  if (tnl) cnl = b0 + tnl;
-  if (tgt) cgt = b0 + tgt;
-  return out;
 }
 
 __global__ __launch_bounds__(256) void k_ss_fa_count(const uint8_t *data, u64 n, const i64 *secs, u64 S, u64 *cnt) {

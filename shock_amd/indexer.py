@@ -131,6 +131,47 @@ def NewLineIndexer(f, n_type="", sn_format="", sn_index_path=""):  # noqa: N802
     return LineIndexer(f, n_type, sn_format, sn_index_path)
 
 
+def CreateMany(indexers, out_paths):  # noqa: N802
+    """Create for many small nodes in one device call: indexers are RecordIndexers or LineIndexers
+    of one kind, out_paths[i] is where indexers[i].create would write.  Their files are read into
+    one host arena and indexed by Context.build_batch_host; then Create's protocol per node, as
+    _GPUIndexer.create follows it: a table goes to <PATH_DATA>/temp and is renamed to out_paths[i];
+    on an error nothing is written to out_paths[i].  -> [(count, "array", err), ...]"""
+    indexers = list(indexers)
+    out_paths = list(out_paths)
+    if len(indexers) != len(out_paths):
+        raise ValueError("CreateMany: one output path per indexer")
+    kinds = {ix.kind for ix in indexers}
+    if len(kinds) > 1 or not kinds <= {"record", "line"}:
+        raise ValueError(f"CreateMany takes record or line indexers of one kind, got {sorted(kinds)}")
+    if not indexers:
+        return []
+    bodies = []
+    for ix in indexers:
+        fd = ix.f.fileno()
+        size = os.fstat(fd).st_size
+        body = b""
+        while len(body) < size:  # pread from offset 0, short reads retried (as shockidx_create reads)
+            piece = os.pread(fd, size - len(body), len(body))
+            if not piece:
+                raise L.ShockIdxError(L.EIO, "unexpected end of file")
+            body += piece
+        bodies.append(body)
+    results = context().build_batch_host(bodies, kind=kinds.pop())
+    tmpdir = os.path.join(PATH_DATA, "temp")
+    os.makedirs(tmpdir, exist_ok=True)
+    out = []
+    for r, path in zip(results, out_paths):
+        if r.status == L.OK:
+            write_idx(r.rows if r.rows is not None else np.zeros((0, 2), np.uint64), tmpdir, path)
+            out.append((r.count, "array", None))
+        elif r.status == L.EFORMAT:
+            out.append((r.count, "array", ShockIndexError(r.err)))
+        else:
+            raise L.ShockIdxError(r.status, (r.err or b"").decode("utf-8", "replace"))
+    return out
+
+
 class ColumnIndexer:
     """index/column.go:15-31: the column indexer holds the file; its own Create is a stub
     (:29-31) and CreateColumnIndex does the work."""
