@@ -24,6 +24,8 @@
  *   shockidx_chunkrecord_subset_device  chunkRecord.Create for subset nodes (chunkrecord.go:100-228)
  *                          with fastq.go:216-243 / fasta.go:143-173 SeekChunk
  *   shockidx_column_device / shockidx_column_fd  CreateColumnIndex: index/column.go:33-130
+ *   shockidx_column_slab_device / shockidx_column_fd_walk  the same loop (column.go:53-108) slab by slab
+ *   shockidx_column_create  CreateColumnIndex with its temp file and rename (column.go:34-40,127)
  *   shockidx_download_plan the section list of a ?download&index=X&part=a&part=b... request, the
  *                          s.R = append(...) loops of controller/node/single.go:372-483 (Idx.Part /
  *                          Idx.Range per part, the subset node's chunkrecord branch :401-425) and
@@ -50,7 +52,9 @@ extern "C" {
  *    Added since without a version change (purely additive): shockidx_column_device,
  *    shockidx_column_fd, shockidx_stream_filter_device, shockidx_download_plan,
  *    shockidx_stream_last_stats, shockidx_build_batch_device, shockidx_build_batch_host,
- *    shockidx_batch_error, shockidx_batch_last_stats */
+ *    shockidx_batch_error, shockidx_batch_last_stats, shockidx_column_carry_bytes,
+ *    shockidx_column_slab_device, shockidx_column_fd_walk, shockidx_column_create (and the code
+ *    SHOCKIDX_EMORE, which only shockidx_column_slab_device returns) */
 #define SHOCKIDX_ABI_VERSION 5
 
 /* index kinds = the registry keys served (index/index.go:21-28) */
@@ -70,6 +74,8 @@ enum shockidx_format {
 enum shockidx_status {
   SHOCKIDX_OK = 0,
   SHOCKIDX_EFORMAT = 1,    /* reader/format error: Go's error string in result.err */
+  SHOCKIDX_EMORE = 2,      /* shockidx_column_slab_device: a line does not close inside the slab's window;
+                              result.state_out is its file offset (the caller's next move, not a failure) */
   SHOCKIDX_EINVAL = -1,
   SHOCKIDX_EHIP = -2,      /* HIP runtime error (result.err holds hipGetErrorString) */
   SHOCKIDX_ENOMEM = -3,
@@ -94,7 +100,8 @@ typedef struct shockidx_result {
   uint32_t path;       /* the build that ran last: 1 tile pass (one read of the input), 2 two-pass,
                           3 slab-pipelined build (build_host of a pinned FASTQ body, build_fd / create),
                           4 the same through two slab slots within the context's device cap
-                          (shockidx_ctx_set_dev_cap) */
+                          (shockidx_ctx_set_dev_cap), 5 the column index in slabs
+                          (shockidx_column_slab_device, shockidx_column_fd_walk; a batch item: the batched walk) */
   uint32_t reruns;     /* builds re-run: a row-capacity overflow, a failed format speculation */
   double index_ms;     /* device time of the main index kernel alone (last pass) */
   uint64_t state_out;  /* format monoid state after the input (slab composition) */
@@ -494,6 +501,59 @@ int shockidx_column_device(shockidx_ctx *ctx, const void *d_data, uint64_t n, in
  * *rows receives a malloc'ed table of result->count rows (free with shockidx_free). */
 int shockidx_column_fd(shockidx_ctx *ctx, int fd, uint64_t n, int column, uint64_t **rows,
                        shockidx_result *result);
+
+/* ---- column index in slabs ------------------------------------------------------------------
+ * The same table built slab by slab, so that the device holds two input slots, one slab's workspace
+ * and one slab's rows however large the node is.  column.go's loop carries four things from line
+ * to line (column.go:44-48): curr (the open group's start), the rows written, line_count != 0 and
+ * prev_str.  A slab takes them from the carry and leaves them in it; nothing else crosses a slab
+ * end.
+ *
+ * The slab (shockidx_slab): d_data 16-byte aligned; n owned bytes, end readable bytes from d_data
+ * (n + halo), front readable bytes before it (at least 16 unless base < 16); base, the file offset
+ * of d_data[0], may be any offset and n any length; is_first: base == 0; is_last: the owned bytes
+ * end the file (base + n == file_size); seq is ignored.  A line belongs to the slab that holds the
+ * '\n' before it, the line at offset 0 to the first slab.  Slabs are submitted in file order; the
+ * first one initialises the carry (d_carry: shockidx_column_carry_bytes() bytes of device memory,
+ * 8-byte aligned, never read by the host: a header and two halves of a state with up to
+ * SHOCKIDX_COLUMN_KEYCAP key bytes -- a slab reads one half and writes the other).
+ *
+ * A slab decides the cut before each non-blank line it owns (column.go:80: its key against the
+ * previous non-blank line's, for its first such line the carried key; before any compared line
+ * prev_str is "" and the line at offset 0 never cuts, :80,99-101) and writes the row each cut closes,
+ * (prev_cut, cut - prev_cut) at file offsets, to d_rows[0 .. count); the last slab also writes the
+ * row that runs to file_size when the file has a cut (:119-125).  The slabs' rows concatenated are
+ * shockidx_column_device's table.
+ *
+ * Returns: SHOCKIDX_OK, count = the rows written.  Any other return leaves the carry as it was and
+ * no row that counts, so the call may be repeated: SHOCKIDX_ESPACE, count = the rows the slab
+ * needs; SHOCKIDX_EFORMAT, the missing-column error (:75-79), count 0 -- the caller drops the rows
+ * of earlier slabs, the reference returns none; SHOCKIDX_EMORE, state_out = the file offset of the
+ * first owned line the slab cannot settle inside [d_data - front, d_data + end): its key does not
+ * close there (for a line with too few fields, or with the key in its last field, its end does
+ * not), or it is the last non-blank owned line of a slab that is not the file's last and its key
+ * is longer than SHOCKIDX_COLUMN_KEYCAP.  When a line without the column and an unsettled line are
+ * both present, the earlier one decides.  No byte outside the window is read.  result->path 5. */
+#define SHOCKIDX_COLUMN_KEYCAP 65536
+uint64_t shockidx_column_carry_bytes(void);
+int shockidx_column_slab_device(shockidx_ctx *ctx, const shockidx_slab *slab, uint64_t file_size, int column,
+                                void *d_carry, void *d_rows, uint64_t row_cap, shockidx_result *result);
+/* The walk over an open descriptor: slab k + 1 crosses PCIe into one slot while slab k is indexed
+ * in the other, each slab's rows go to the host as they are made.  slab_bytes 0: sized so that the
+ * slots, the workspace and the rows fit the context's device budget (shockidx_ctx_set_dev_cap, at
+ * least 32 MiB); halo_bytes 0: 4 MiB (a sixteenth of a budget under 64 MiB).  SHOCKIDX_EMORE from a
+ * slab at offset x: the slab is submitted again as [base, x - 1) and the next one starts at x - 1;
+ * when x - 1 is the slab's base, no slot can hold the line or key: SHOCKIDX_ENOMEM.  result->reruns
+ * counts the slabs submitted again.  shockidx_column_fd takes this walk when the whole node, its
+ * workspace and its rows do not fit the budget. */
+int shockidx_column_fd_walk(shockidx_ctx *ctx, int fd, uint64_t n, int column, uint64_t slab_bytes,
+                            uint64_t halo_bytes, uint64_t **rows, shockidx_result *result);
+/* CreateColumnIndex's file protocol (column.go:36-44,109-129): the table into a temp file under
+ * tmpdir, renamed to outpath; a file of one group leaves a zero-byte file.  Within the budget the
+ * whole-node build, else the walk, whose rows are written at 16 * row as each slab delivers them.
+ * On any error nothing is left at outpath or in tmpdir. */
+int shockidx_column_create(shockidx_ctx *ctx, int fd, uint64_t n, int column, const char *tmpdir,
+                           const char *outpath, shockidx_result *result);
 
 /* ---- The batch build: many small nodes indexed in one call -----------------------------------
  * A batch is a list of nnodes nodes {int64 pos, int64 len} (the layout of the stream's sections) of

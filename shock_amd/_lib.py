@@ -23,6 +23,8 @@ FMT_CODES = {"fasta": FMT_FASTA, "fastq": FMT_FASTQ, "sam": FMT_SAM, "line": FMT
 PLAN_PART, PLAN_RANGE, PLAN_CHUNK_RANGE, PLAN_SIZE = 0, 1, 2, 3  # shockidx_plan_mode
 
 OK, EFORMAT, EINVAL, EHIP, ENOMEM, EIO, EINTERNAL, ESPACE = 0, 1, -1, -2, -3, -4, -5, -6
+EMORE = 2  # column_slab: a line does not close inside the slab's window (state_out: its file offset)
+COLUMN_KEYCAP = 65536  # SHOCKIDX_COLUMN_KEYCAP
 
 EXPORTS = ("shockidx_ctx_create", "shockidx_ctx_destroy", "shockidx_build_device",
            "shockidx_build_host", "shockidx_host_register", "shockidx_host_unregister", "shockidx_build_fd", "shockidx_create", "shockidx_write_idx",
@@ -33,7 +35,8 @@ EXPORTS = ("shockidx_ctx_create", "shockidx_ctx_destroy", "shockidx_build_device
            "shockidx_comm_allgather", "shockidx_comm_destroy", "shockidx_comm_count", "shockidx_subset_index", "shockidx_subset_gather",
            "shockidx_subset_node",
            "shockidx_chunkrecord_device", "shockidx_chunkrecord_fd", "shockidx_chunkrecord_subset_device", "shockidx_create_subset_index",
-           "shockidx_column_device", "shockidx_column_fd",
+           "shockidx_column_device", "shockidx_column_fd", "shockidx_column_carry_bytes", "shockidx_column_slab_device",
+           "shockidx_column_fd_walk", "shockidx_column_create",
            "shockidx_idx_part", "shockidx_idx_range", "shockidx_filter_device", "shockidx_stream_filter_device", "shockidx_stream_last_stats",
            "shockidx_build_batch_device", "shockidx_build_batch_host", "shockidx_batch_error", "shockidx_batch_last_stats",
            "shockidx_download_plan", "shockidx_ctx_trim",
@@ -148,6 +151,14 @@ def lib():
     L.shockidx_column_device.restype = i32
     L.shockidx_column_fd.argtypes = [vp, i32, u64, i32, PPu64, PRes]
     L.shockidx_column_fd.restype = i32
+    L.shockidx_column_carry_bytes.argtypes = []
+    L.shockidx_column_carry_bytes.restype = u64
+    L.shockidx_column_slab_device.argtypes = [vp, ctypes.POINTER(Slab), u64, i32, vp, vp, u64, PRes]
+    L.shockidx_column_slab_device.restype = i32
+    L.shockidx_column_fd_walk.argtypes = [vp, i32, u64, i32, u64, u64, PPu64, PRes]
+    L.shockidx_column_fd_walk.restype = i32
+    L.shockidx_column_create.argtypes = [vp, i32, u64, i32, ctypes.c_char_p, ctypes.c_char_p, PRes]
+    L.shockidx_column_create.restype = i32
     L.shockidx_build_host.argtypes = [vp, vp, u64, i32, i32, PPu64, PRes]
     L.shockidx_build_host.restype = i32
     L.shockidx_host_register.argtypes = [vp, vp, u64]

@@ -343,6 +343,41 @@ class Context:
             d_in.free()
             d_rows.free()
 
+    # -- column index in slabs (shockidx_column_slab_device and the walk over it) -----------------
+    def column_carry(self) -> "DeviceBuffer":
+        """Device memory for the carry of one slab walk (shockidx_column_carry_bytes; the first slab
+        initialises it)."""
+        return self.alloc(int(self._lib.shockidx_column_carry_bytes()))
+
+    def column_slab(self, slab: "L.Slab", file_size: int, column: int, d_carry: int, d_rows: int,
+                    row_cap: int) -> IndexResult:
+        """One slab of the column index (slabs go in file order, the carry between them on the device).
+        OK: count rows at file offsets in d_rows; ESPACE: count = the rows the slab needs; EFORMAT: the
+        missing-column error; EMORE: state_out = the file offset of the first owned line the slab's
+        window cannot settle.  Anything but OK leaves the carry untouched."""
+        res = L.Result()
+        rc = self._lib.shockidx_column_slab_device(self._h, ctypes.byref(slab), file_size, column, d_carry, d_rows,
+                                                   row_cap, ctypes.byref(res))
+        return _result(res, rc)
+
+    def column_fd_walk(self, fd: int, size: int, column: int, slab_bytes: int = 0, halo_bytes: int = 0) -> IndexResult:
+        """CreateColumnIndex over an open file, always slab by slab (shockidx_column_fd_walk; 0: slabs
+        sized to the device budget, a 4 MiB halo); rows on the host, path 5."""
+        res = L.Result()
+        rows_p = ctypes.POINTER(ctypes.c_uint64)()
+        rc = self._lib.shockidx_column_fd_walk(self._h, fd, size, column, slab_bytes, halo_bytes, ctypes.byref(rows_p),
+                                               ctypes.byref(res))
+        rows = _take_rows(rows_p, int(res.count)) if rows_p else None
+        return _result(res, rc, rows)
+
+    def column_create(self, fd: int, size: int, column: int, tmpdir: str, outpath: str) -> IndexResult:
+        """CreateColumnIndex with its file protocol (shockidx_column_create): the table through a temp
+        file under tmpdir to outpath; on an error neither is left behind."""
+        res = L.Result()
+        rc = self._lib.shockidx_column_create(self._h, fd, size, column, os.fsencode(tmpdir), os.fsencode(outpath),
+                                              ctypes.byref(res))
+        return _result(res, rc)
+
     def set_dev_cap(self, nbytes: int) -> None:
         """Device bytes one fd build may hold (shockidx_ctx_set_dev_cap; 0: what is free).  A node
         whose one-pass build would not fit is indexed through two slab slots sized to the cap."""

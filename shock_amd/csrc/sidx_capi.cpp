@@ -371,6 +371,51 @@ int shockidx_create(shockidx_ctx *c, int fd, uint64_t n, int kind, const char *t
   return SHOCKIDX_OK;
 }
 
+// CreateColumnIndex's file protocol (column.go:34-40,109-129).  Within the device budget: the
+// whole-node build, its table written in one piece.  Else the slab walk, each slab's rows written
+// at 16 * row as they arrive; whatever ends the walk early -- the missing-column line may sit in
+// the last slab, after rows were written -- takes the temp file with it.
+int shockidx_column_create(shockidx_ctx *c, int fd, uint64_t n, int column, const char *tmpdir, const char *outpath,
+                           shockidx_result *res) {
+  shockidx_result tmp;
+  if (!res) res = &tmp;
+  reset_result(res);
+  res->format = SHOCKIDX_FMT_LINE;
+  if (!c || fd < 0 || column < 1 || !tmpdir || !outpath) return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  if (column_whole_bytes(n) <= dev_budget(c)) {
+    uint64_t *rows = nullptr;
+    const int rc = shockidx_column_fd(c, fd, n, column, &rows, res);
+    if (rc != SHOCKIDX_OK) {
+      free(rows);
+      return rc;
+    }
+    const double t0 = now_ms();
+    const int w = shockidx_write_idx(rows, res->count, tmpdir, outpath, res->err, sizeof res->err);
+    free(rows);
+    if (w != SHOCKIDX_OK) return set_msg(res, w, res->err);
+    res->total_ms += now_ms() - t0;
+    return SHOCKIDX_OK;
+  }
+  TrimGuard trim{c};
+  FileSink sink;
+  const std::string tpath = temp_idx_path(tmpdir);
+  sink.fd = open(tpath.c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0666);
+  if (sink.fd < 0) return set_msg(res, SHOCKIDX_EIO, std::string("create: ") + strerror(errno));
+  const int rc = column_fd_walk(c, fd, n, (u32)column, 0, 0, sink, res);
+  const int ce = close(sink.fd);
+  if (rc != SHOCKIDX_OK) {
+    unlink(tpath.c_str());
+    return rc;
+  }
+  if (ce != 0 || rename(tpath.c_str(), outpath) != 0) {  // column.go:127
+    const int e = errno;
+    unlink(tpath.c_str());
+    return set_msg(res, SHOCKIDX_EIO, std::string(ce != 0 ? "close: " : "rename: ") + strerror(e));
+  }
+  return SHOCKIDX_OK;
+}
+
 int shockidx_dev_alloc(shockidx_ctx *c, uint64_t bytes, void **d_ptr) {
   if (!c || !d_ptr) return SHOCKIDX_EINVAL;
   if (hipSetDevice(c->device) != hipSuccess) return SHOCKIDX_EHIP;

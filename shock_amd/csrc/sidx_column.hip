@@ -32,6 +32,22 @@
 //   (sum scan)    each tile's first cut number
 //   k_col_place   cut k's offset into row k + 1
 //   k_col_lens    row 0's offset and every length
+//
+// The slab pass is the tile pass over one slab of the file (n owned bytes, a halo readable past
+// them), with what column.go's loop carries from line to line (column.go:44-48: curr, the rows so
+// far, line_count != 0, prev_str) in a carry on the device:
+//
+//   k_col_tiles        as above, without line 0 unless the slab starts the file and without a
+//                      "last piece" unless its owned bytes end it
+//   k_col_fix<true>    bounded by the slab's readable end; a tile's first line without a
+//                      predecessor in the slab is compared with the carried key (column.go:80);
+//                      a line whose key does not close in the window is reported, not guessed
+//   k_col_slab_sum     the cut total, the last non-blank owned line and its key, the rows
+//   (host stop)        first bad line, first unsettled line, rows against the capacity
+//   k_col_slab_place   cut k ends row k and starts row k + 1, at file offsets
+//   k_col_slab_close   row k = (its start: row 0's is the carried cut, its length); the file's last
+//                      slab closes the last row at the file's size (column.go:119-125)
+//   k_col_slab_carry   the next carry into the half this slab did not read, then the flip
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -94,17 +110,20 @@ __device__ bool col_key(const uint8_t *d, u64 n, u64 off, u64 len, u32 c, u64 &l
 
 // bytes [a, a + len) differ from [b, b + len): the 16-byte pieces first, first + stride, ...
 // (one lane: 0 and 16; a wave: 16 * lane and 1024)
-__device__ bool col_differ(const uint8_t *d, u64 a, u64 b, u64 len, u64 first, u64 stride) {
+__device__ bool col_differ2(const uint8_t *pa, const uint8_t *pb, u64 len, u64 first, u64 stride) {
   for (u64 m = first; m < len; m += stride) {
     if (len - m >= 16) {
-      const uint4 x = col_load16u(d + a + m), y = col_load16u(d + b + m);
+      const uint4 x = col_load16u(pa + m), y = col_load16u(pb + m);
       if ((x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w)) return true;
     } else {
       for (u64 i = m; i < len; ++i)
-        if (d[a + i] != d[b + i]) return true;
+        if (pa[i] != pb[i]) return true;
     }
   }
   return false;
+}
+__device__ __forceinline__ bool col_differ(const uint8_t *d, u64 a, u64 b, u64 len, u64 first, u64 stride) {
+  return col_differ2(d + a, d + b, len, first, stride);
 }
 
 __global__ __launch_bounds__(COL_T) void k_col_flags(const u64 *lt, u64 L, u32 *flag, u64 *ctl) {
@@ -262,12 +281,16 @@ __global__ __launch_bounds__(SNT, SIDX_COL_WGS) void k_col_tiles(const SlabParam
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const u64 G = p.pgrid;
   const uint8_t *tb = raw + FRONT;
+  const u64 fend = (p.eof && p.n == p.end) ? p.n : ~0ull;  // where the owned bytes end the file (a slab's may not)
+  const u64 flast = p.eof ? p.end - 1 : ~0ull;             // the file's last byte, if the slab can read it
   for (u64 t = first_tile(blockIdx.x, G); t < p.ntiles; t += G) {
     stage_tile<false>(p, t, (u32)(size_t)(lds_u8 *)raw, wid, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const u64 tlo = t * TILE;
     const u32 tlen = (u32)(((tlo + TILE < p.n) ? tlo + TILE : p.n) - tlo);
-    const bool last_tile = tlo + tlen == p.n;
+    // the tile ends the file (a slab whose owned bytes stop before the file does has no such tile:
+    // the lines that leave its last tile end in its halo, or later)
+    const bool last_tile = tlo + tlen == fend;
     u64 mnl = 0, mtb = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -322,8 +345,9 @@ __global__ __launch_bounds__(SNT, SIDX_COL_WGS) void k_col_tiles(const SlabParam
       }
       if (!found) {
         if (!last_tile) {  // it ends in a later tile: blank only if it starts there with "\n" or as the file's last byte
-          const u64 a = tlo + TILE;
-          if (s < tlen || (p.data[a] != '\n' && a + 1 != p.n)) xS = s;
+          // (a slab without a readable byte there cannot tell: the line goes to k_col_fix, which reports it)
+          const u64 a = tlo + tlen;
+          if (s < tlen || a >= p.end || (p.data[a] != '\n' && a != flast)) xS = s;
           return;
         }
         e = tlen;  // the file's last piece
@@ -343,7 +367,7 @@ __global__ __launch_bounds__(SNT, SIDX_COL_WGS) void k_col_tiles(const SlabParam
       pLo = lo;
       pLen = klen;
     };
-    if (t == 0 && tid == 0) do_line(0, -1);
+    if (t == 0 && tid == 0 && p.file_start) do_line(0, -1);
     for (u64 b = mnl; b; b &= b - 1) {
       const int bit = (int)ctz64(b);
       do_line((u32)tid * 64 + (u32)bit + 1, bit);
@@ -397,8 +421,13 @@ __global__ __launch_bounds__(SNT, SIDX_COL_WGS) void k_col_tiles(const SlabParam
 }
 
 // col_key for the line that starts at s, its end not known: the scan stops at the line's '\n'
-__device__ bool col_key_open(const uint8_t *d, u64 n, u64 s, u32 c, u64 &lo, u64 &klen) {
+// kWin: d[n) is where a slab's readable bytes end, the file's end only with eof; a line that reaches
+// it with neither its key's closing '\t' nor its '\n' is CK_OPEN (the slab cannot settle it)
+enum ColKeyState : u32 { CK_OK = 0, CK_BAD = 1, CK_OPEN = 2 };
+template <bool kWin>
+__device__ u32 col_key_scan(const uint8_t *d, u64 n, bool eof, u64 s, u32 c, u64 &lo, u64 &klen) {
   u64 t = 0, end = n;
+  bool closed = false;
   lo = s;
   for (u64 a = s & ~15ull; a < end; a += 16) {
     const uint4 v = col_load16(d, a, n);
@@ -410,29 +439,38 @@ __device__ bool col_key_open(const uint8_t *d, u64 n, u64 s, u32 c, u64 &lo, u64
     if (ml) {  // the line ends here: tabs up to its '\n' only
       end = a + (u32)__builtin_ctz(ml) + 1;
       m &= (1u << (u32)(end - a)) - 1u;
+      closed = true;
     }
     while (m) {
       const u64 pos = a + (u32)__builtin_ctz(m);
       m &= m - 1;
       if (++t == c) {
         klen = pos - lo;
-        return true;
+        return CK_OK;
       }
       if (t + 1 == c) lo = pos + 1;
     }
   }
-  if (t + 1 < c) {
-    klen = 0;
-    return false;
-  }
+  klen = 0;
+  if (kWin && !closed && !eof) return CK_OPEN;
+  if (t + 1 < c) return CK_BAD;
   klen = end - lo;
-  return true;
+  return CK_OK;
+}
+__device__ bool col_key_open(const uint8_t *d, u64 n, u64 s, u32 c, u64 &lo, u64 &klen) {
+  return col_key_scan<false>(d, n, true, s, c, lo, klen) == CK_OK;
 }
 
 // thread 2 t + j: undecided line j of tile t against its predecessor (j = 0: the last non-blank
 // line before the tile, pprev; none: prev_str is "" and line 0 never cuts), from global memory
+// kSlab: d[n) is where the slab's readable bytes end (sa.eof: the file's); a line whose key does
+// not close before it is reported in COLS_MORE; offsets are the slab's, sa.base the file's of d[0];
+// and a tile's first line without a predecessor in the slab is compared with the carried key
+// (none carried yet: prev_str is "", and the line at file offset 0 never cuts)
+template <bool kSlab>
 __global__ __launch_bounds__(COL_T) void k_col_fix(const uint8_t *d, u64 n, u64 ntiles, u32 c, const u64 *tword,
-                                                   const u64 *pprev, u32 *fcut, u32 *tot, u64 *ctl) {
+                                                   const u64 *pprev, u32 *fcut, u32 *tot, u64 *ctl,
+                                                   const ColSlabArgs sa) {
   const u64 i = (u64)blockIdx.x * COL_T + threadIdx.x;
   const int lane = threadIdx.x & 63;
   const u64 t = i >> 1;
@@ -443,24 +481,39 @@ __global__ __launch_bounds__(COL_T) void k_col_fix(const uint8_t *d, u64 n, u64 
   u32 cut = 0;
   bool wide = false;
   u64 a = 0, b = 0, len = 0;
+  const uint8_t *pb = d;  // the predecessor's key is pb[b ..)
   if (valid && ds != CT_NONE) {
     const u64 tlo = t * TILE, s = tlo + ds;
     const u64 pp = j ? tlo + ((u32)(w >> 48) & 0xFFFFu) + 1 : pprev[t];  // predecessor start + 1, 0: none
-    if (!col_key_open(d, n, s, c, a, len)) atomicMin(&ctl[COL_BAD], s);
-    if (!pp) {
-      cut = (s != 0 && len != 0) ? 1u : 0u;
+    u64 plen = 0;
+    bool have = pp != 0;
+    if (kSlab) {
+      const u32 st = col_key_scan<true>(d, n, sa.eof != 0, s, c, a, len);
+      if (st == CK_BAD) atomicMin(&ctl[COL_BAD], s);
+      if (st == CK_OPEN) atomicMin(&ctl[COLS_MORE], s);
+      if (pp) {
+        (void)col_key_scan<true>(d, n, sa.eof != 0, pp - 1, c, b, plen);
+      } else if (!sa.first) {
+        const ColCarryHalf *h = &sa.carry->half[sa.carry->cur & 1];
+        if (h->seen) {
+          have = true;
+          pb = h->key;
+          plen = h->klen;
+        }
+      }
     } else {
-      u64 plen;
-      (void)col_key_open(d, n, pp - 1, c, b, plen);
-      if (len != plen) cut = 1;
-      else if (len > COL_WAVE_KEY) wide = true;
-      else cut = col_differ(d, a, b, len, 0, 16) ? 1u : 0u;
+      if (!col_key_open(d, n, s, c, a, len)) atomicMin(&ctl[COL_BAD], s);
+      if (pp) (void)col_key_open(d, n, pp - 1, c, b, plen);
     }
+    if (!have) cut = ((kSlab ? sa.base + s : s) != 0 && len != 0) ? 1u : 0u;
+    else if (len != plen) cut = 1;
+    else if (len > COL_WAVE_KEY) wide = true;
+    else cut = col_differ2(d + a, pb + b, len, 0, 16) ? 1u : 0u;
   }
   for (u64 wm = __ballot(wide); wm; wm &= wm - 1) {  // (every lane of the wave is here)
     const int src = (int)ctz64(wm);
-    const u64 wa = __shfl(a, src, 64), wb = __shfl(b, src, 64), wl = __shfl(len, src, 64);
-    const bool df = col_differ(d, wa, wb, wl, (u64)lane * 16, 1024);
+    const u64 wa = __shfl((u64)(d + a), src, 64), wb = __shfl((u64)(pb + b), src, 64), wl = __shfl(len, src, 64);
+    const bool df = col_differ2((const uint8_t *)wa, (const uint8_t *)wb, wl, (u64)lane * 16, 1024);
     if (__ballot(df) && lane == src) cut = 1;
   }
   const u32 other = (u32)__shfl_xor((int)cut, 1, 64);
@@ -500,6 +553,95 @@ __global__ __launch_bounds__(COL_T) void k_col_lens(u64 *rows, u64 count, u64 n)
   const u64 off = k ? rows[2 * k] : 0, next = k + 1 < count ? rows[2 * (k + 1)] : n;
   if (!k) rows[0] = 0;
   rows[2 * k + 1] = next - off;
+}
+
+// ====================================================================================
+// The slab pass: the tile pass over one slab of the file, column.go's loop state carried in
+// ====================================================================================
+__device__ __forceinline__ const ColCarryHalf *col_carry_in(const ColSlabArgs &sa) {
+  return sa.first ? nullptr : &sa.carry->half[sa.carry->cur & 1];
+}
+
+__global__ void k_col_slab_init(u64 *ctl) {
+  if (threadIdx.x < COL_SLAB_WORDS) ctl[threadIdx.x] = (threadIdx.x == COL_BAD || threadIdx.x == COLS_MORE) ? ~0ull : 0ull;
+}
+
+// After the cut scan, one thread: the slab's cuts, its last non-blank owned line and that line's
+// key (what the next slab compares its first line with; longer than a carry holds: the slab
+// cannot settle it, unless no slab follows), and the rows it writes -- one per cut, and in the
+// file's last slab the row that runs to the file's end when the file has a cut (column.go:119-125)
+__global__ void k_col_slab_sum(const uint8_t *d, const ColSlabArgs sa, u64 ntiles, u32 c, const u64 *cbase,
+                               const u32 *tot, const u64 *pprev, const u64 *plast, u64 *ctl) {
+  if (threadIdx.x != 0) return;
+  u64 B = 0, L = 0, klo = 0, klen = 0;
+  if (ntiles) {
+    B = cbase[ntiles - 1] + tot[ntiles - 1];
+    const u64 x = pprev[ntiles - 1], y = plast[ntiles - 1];
+    L = x > y ? x : y;
+  }
+  if (L && ctl[COL_BAD] == ~0ull && ctl[COLS_MORE] == ~0ull) {
+    const u32 st = col_key_scan<true>(d, sa.end, sa.eof != 0, L - 1, c, klo, klen);
+    if (st != CK_OK || (klen > COL_KEYCAP && !sa.last)) ctl[COLS_MORE] = L - 1;
+  }
+  const ColCarryHalf *h = col_carry_in(sa);
+  const u64 before = h ? h->rows : 0;
+  ctl[COL_B] = B;
+  ctl[COLS_LAST] = L;
+  ctl[COLS_KLO] = klo;
+  ctl[COLS_KLEN] = klen;
+  ctl[COLS_ROWS] = B + ((sa.last && before + B) ? 1u : 0u);
+}
+
+// one wave per tile, as k_col_place: cut k of the slab ends row k and starts row k + 1 (file offsets)
+__global__ __launch_bounds__(COL_T) void k_col_slab_place(u64 ntiles, u64 base, const u64 *tword, const u32 *fcut,
+                                                          const u64 *cbase, const uint16_t *cslot, u64 *rows,
+                                                          u64 nrows) {
+  const u64 t = ((u64)blockIdx.x * COL_T + threadIdx.x) >> 6;
+  const u32 lane = threadIdx.x & 63;
+  if (t >= ntiles) return;
+  const u64 w = tword[t], tlo = base + t * TILE, cb = cbase[t];
+  const u32 cnt = (u32)w & 0xFFFFu, f0 = fcut[2 * t], f1 = fcut[2 * t + 1];
+  auto put = [&](u64 k, u64 off) {
+    if (k < nrows) rows[2 * k + 1] = off;
+    if (k + 1 < nrows) rows[2 * (k + 1)] = off;
+  };
+  if (lane == 0 && f0) put(cb, tlo + ((u32)(w >> 16) & 0xFFFFu));
+  for (u32 j = lane; j < cnt; j += 64) put(cb + f0 + j, tlo + cslot[t * COL_CSLOT + j]);
+  if (lane == 0 && f1) put(cb + f0 + cnt, tlo + ((u32)(w >> 32) & 0xFFFFu));
+}
+
+// row k of the slab from the ends k_col_slab_place left: it starts at the cut before it (row 0:
+// the carried one) and ends at its cut (the row after the slab's last cut: at the file's end)
+__global__ __launch_bounds__(COL_T) void k_col_slab_close(const ColSlabArgs sa, const u64 *ctl, u64 *rows, u64 nrows) {
+  const u64 k = (u64)blockIdx.x * COL_T + threadIdx.x;
+  if (k >= nrows) return;
+  const ColCarryHalf *h = col_carry_in(sa);
+  const u64 off = k ? rows[2 * k] : (h ? h->prev_cut : 0ull);
+  const u64 end = k < ctl[COL_B] ? rows[2 * k + 1] : sa.file_size;
+  reinterpret_cast<ulonglong2 *>(rows)[k] = make_ulonglong2(off, end - off);
+}
+
+// The carry after the slab, into the half the slab did not read; then that half becomes current.
+// One workgroup: the key of the slab's last non-blank owned line (none: the carried one again).
+__global__ __launch_bounds__(COL_T) void k_col_slab_carry(const uint8_t *d, const ColSlabArgs sa, ColCarry *carry,
+                                                          const u64 *ctl, const u64 *rows, u64 nrows) {
+  const u32 cur = sa.first ? 1u : (u32)(carry->cur & 1);
+  const ColCarryHalf *h = col_carry_in(sa);
+  ColCarryHalf *o = &carry->half[cur ^ 1u];
+  const u64 B = ctl[COL_B], L = ctl[COLS_LAST];
+  const uint8_t *src = L ? d + ctl[COLS_KLO] : (h ? h->key : d);
+  u64 klen = L ? ctl[COLS_KLEN] : (h && h->seen ? h->klen : 0ull);
+  if (klen > COL_KEYCAP) klen = COL_KEYCAP;  // (the file's last slab: nothing reads this carry)
+  for (u64 i = threadIdx.x; i < klen; i += COL_T) o->key[i] = src[i];
+  if (threadIdx.x == 0) {
+    o->prev_cut = B ? rows[2 * (B - 1)] + rows[2 * (B - 1) + 1] : (h ? h->prev_cut : 0ull);
+    o->rows = (h ? h->rows : 0ull) + nrows;
+    o->seen = (L || (h && h->seen)) ? 1ull : 0ull;
+    o->klen = klen;
+  }
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0) carry->cur = cur ^ 1u;
 }
 
 }  // namespace sidx
@@ -602,8 +744,8 @@ extern "C" hipError_t sidx_col_tile_cuts(const uint8_t *d, u64 n, u32 column, u3
   size_t sb = w.scan_bytes;
   hipError_t e = dscan::run<u64, dscan::Max, true>(w.scan_tmp, &sb, (const u64 *)w.plast, w.pprev, nt, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_col_fix, dim3(nblk(2 * nt)), dim3(COL_T), 0, s, d, n, nt, column, w.tword, w.pprev, w.fcut, w.tot,
-                     w.ctl);
+  hipLaunchKernelGGL(k_col_fix<false>, dim3(nblk(2 * nt)), dim3(COL_T), 0, s, d, n, nt, column, w.tword, w.pprev, w.fcut,
+                     w.tot, w.ctl, ColSlabArgs{});
   e = dscan::run<u32, dscan::Sum, true>(w.scan_tmp, &sb, (const u32 *)w.tot, w.cbase, nt, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_col_total, dim3(1), dim3(64), 0, s, w.cbase, w.tot, nt, w.ctl);
@@ -617,5 +759,54 @@ extern "C" hipError_t sidx_col_tile_rows(u64 n, void *ws, u64 count, u64 *rows, 
   hipLaunchKernelGGL(k_col_place, dim3(nblk(64 * nt)), dim3(COL_T), 0, s, nt, w.tword, w.fcut, w.cbase, w.cslot, rows,
                      row_cap);
   hipLaunchKernelGGL(k_col_lens, dim3(nblk(count)), dim3(COL_T), 0, s, rows, count, n);
+  return hipGetLastError();
+}
+
+// ---- the slab pass -------------------------------------------------------------------
+// One slab up to its host stop (sl: the slab, sa.carry: the carry it reads): *ctl_out = the
+// COL_SLAB_WORDS control words in ws (sidx_col_tile_bytes(tiles of sl.n) bytes).
+extern "C" hipError_t sidx_col_slab_cuts(const uint8_t *d, u64 n, u64 front, const ColSlabArgs *sa, u32 column, u32 grid,
+                                         void *ws, const u64 **ctl_out, hipStream_t s) {
+  const u64 nt = (n + TILE - 1) / TILE;
+  const ColTileWs w = col_tile_carve(ws, nt ? nt : 1);
+  *ctl_out = w.ctl;
+  hipLaunchKernelGGL(k_col_slab_init, dim3(1), dim3(64), 0, s, w.ctl);
+  if (nt) {
+    SlabParams p;
+    memset(&p, 0, sizeof p);
+    p.data = d;
+    p.n = n;
+    p.end = sa->end;
+    p.front = front;
+    p.base = sa->base;
+    p.ntiles = (u32)nt;
+    p.pgrid = grid && grid < nt ? grid : (u32)nt;
+    p.eof = sa->eof;
+    p.file_start = sa->first;
+    hipLaunchKernelGGL(k_col_tiles, dim3(p.pgrid), dim3(SNT), 0, s, p, column, w.tword, w.plast, w.cslot, w.ctl);
+    size_t sb = w.scan_bytes;
+    hipError_t e = dscan::run<u64, dscan::Max, true>(w.scan_tmp, &sb, (const u64 *)w.plast, w.pprev, nt, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_col_fix<true>, dim3(nblk(2 * nt)), dim3(COL_T), 0, s, d, sa->end, nt, column, w.tword, w.pprev,
+                       w.fcut, w.tot, w.ctl, *sa);
+    e = dscan::run<u32, dscan::Sum, true>(w.scan_tmp, &sb, (const u32 *)w.tot, w.cbase, nt, s);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_col_slab_sum, dim3(1), dim3(64), 0, s, d, *sa, nt, column, w.cbase, w.tot, w.pprev, w.plast, w.ctl);
+  return hipGetLastError();
+}
+
+// the slab's nrows rows (nrows <= the capacity of rows) and the carry after it
+extern "C" hipError_t sidx_col_slab_rows(const uint8_t *d, u64 n, const ColSlabArgs *sa, void *ws, ColCarry *carry,
+                                         u64 *rows, u64 nrows, hipStream_t s) {
+  const u64 nt = (n + TILE - 1) / TILE;
+  const ColTileWs w = col_tile_carve(ws, nt ? nt : 1);
+  if (nrows) {
+    if (nt)
+      hipLaunchKernelGGL(k_col_slab_place, dim3(nblk(64 * nt)), dim3(COL_T), 0, s, nt, sa->base, w.tword, w.fcut, w.cbase,
+                         w.cslot, rows, nrows);
+    hipLaunchKernelGGL(k_col_slab_close, dim3(nblk(nrows)), dim3(COL_T), 0, s, *sa, w.ctl, rows, nrows);
+  }
+  hipLaunchKernelGGL(k_col_slab_carry, dim3(1), dim3(COL_T), 0, s, d, *sa, carry, w.ctl, rows, nrows);
   return hipGetLastError();
 }

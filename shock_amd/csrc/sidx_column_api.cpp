@@ -1,6 +1,7 @@
 // sidx_column_api.cpp -- the column index entry points of the C ABI (index/column.go:33-130,
 // called from node/index.go:43-54) over sidx_column.hip: the tile pass, or the general build
-// over the line index of the bytes.
+// over the line index of the bytes; and the same loop (column.go:53-108) one slab at a time, its
+// state (column.go:44-48) in a device carry, for nodes that do not fit the device budget.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -120,6 +121,58 @@ int column_build(shockidx_ctx *c, const uint8_t *dd, u64 n, u32 column, bool own
 
 }  // namespace
 
+namespace sidx_host {
+
+u64 column_whole_bytes(u64 n) {
+  const u64 node = n + 64, tb = sidx_col_tile_bytes((n + TILE - 1) / TILE), rows = 16 * (n / 32 + 4096);
+  return node + node / 8 + tb + tb / 8 + rows + rows / 8 + (1ull << 20);
+}
+
+// column.go:64-101 over one slab: the tile pass bounded by the slab's window, one host stop (the
+// first line without the column, the first line the window cannot settle, the rows), then the
+// rows against the carried cut and the carry for the next slab.
+int column_slab_run(shockidx_ctx *c, const ColSlabIn &sl, u32 column, void *ws, ColCarry *carry, u64 *d_rows,
+                    u64 row_cap, hipStream_t s, shockidx_result *res) {
+  res->path = 5;
+  res->format = SHOCKIDX_FMT_LINE;
+  ColSlabArgs sa;
+  memset(&sa, 0, sizeof sa);
+  sa.end = sl.end;
+  sa.base = sl.base;
+  sa.file_size = sl.file_size;
+  sa.carry = carry;
+  sa.eof = sl.base + sl.end == sl.file_size;
+  sa.first = sl.first;
+  sa.last = sl.last;
+  const u64 *ctl = nullptr;
+  HIPCHK(hipEventRecord(c->ev0, s), "event");
+  HIPCHK(sidx_col_slab_cuts(sl.d, sl.n, sl.front, &sa, column, c->tiles_grid, ws, &ctl, s), "column slab launch");
+  HIPCHK(hipMemcpyAsync(c->h_det, ctl, COL_SLAB_WORDS * sizeof(u64), hipMemcpyDeviceToHost, s), "column copy");
+  HIPCHK(hipStreamSynchronize(s), "column sync");
+  u64 h[COL_SLAB_WORDS];
+  memcpy(h, c->h_det, sizeof h);
+  // the earlier of the two lines decides (a bad line after an unsettled one may be the unsettled
+  // line's own tail)
+  if (h[COLS_MORE] != ~0ull && h[COLS_MORE] < h[COL_BAD]) {
+    res->state_out = sl.base + h[COLS_MORE];
+    return set_msg(res, SHOCKIDX_EMORE, "a line of the slab does not close inside its window");
+  }
+  if (h[COL_BAD] != ~0ull) return set_msg(res, SHOCKIDX_EFORMAT, COLUMN_MISSING);
+  const u64 nrows = h[COLS_ROWS];
+  res->count = nrows;
+  if (nrows > row_cap) return set_msg(res, SHOCKIDX_ESPACE, "row capacity too small");
+  HIPCHK(sidx_col_slab_rows(sl.d, sl.n, &sa, ws, carry, d_rows, nrows, s), "column rows launch");
+  HIPCHK(hipEventRecord(c->ev1, s), "event");
+  HIPCHK(hipStreamSynchronize(s), "column sync");
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+  res->kernel_ms += ms;
+  res->index_ms = res->kernel_ms;
+  return SHOCKIDX_OK;
+}
+
+}  // namespace sidx_host
+
 extern "C" {
 
 // CreateColumnIndex (index/column.go:33-130).  The first non-blank line with fewer than `column`
@@ -154,10 +207,57 @@ int shockidx_column_fd(shockidx_ctx *c, int fd, uint64_t n, int column, uint64_t
   TrimGuard trim{c};
   const double t0 = now_ms();
   HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  if (column_whole_bytes(n) > dev_budget(c)) return shockidx_column_fd_walk(c, fd, n, column, 0, 0, rows, res);
   if (int rc = stage_fd(c, fd, 0, n, c->stream, res)) return rc;
   if (int rc = column_build(c, c->d_in, n, (u32)column, true, nullptr, 0, c->stream, res)) return rc;
   if (int rc = fetch_rows(c, res->count, c->stream, rows, res)) return rc;
   res->total_ms = now_ms() - t0;
+  return SHOCKIDX_OK;
+}
+
+uint64_t shockidx_column_carry_bytes(void) { return sizeof(ColCarry); }
+
+// One slab of the column index (column.go:64-101 with its loop state carried from slab to slab).
+int shockidx_column_slab_device(shockidx_ctx *c, const shockidx_slab *slab, uint64_t file_size, int column,
+                                void *d_carry, void *d_rows, uint64_t row_cap, shockidx_result *res) {
+  shockidx_result tmp;
+  if (!res) res = &tmp;
+  reset_result(res);
+  res->format = SHOCKIDX_FMT_LINE;
+  if (!c || !slab || !d_carry || (!d_rows && row_cap) || column < 1) return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+  const shockidx_slab &b = *slab;
+  const bool first = b.base == 0, last = b.base + b.n == file_size;
+  if (b.end < b.n || b.base > file_size || b.end > file_size - b.base || (!b.n && file_size) ||
+      (b.n && (!b.d_data || ((uintptr_t)b.d_data & 15))) || (b.is_first != 0) != first || (b.is_last != 0) != last ||
+      (b.front < 16 && b.base >= 16) || b.front > b.base || ((uintptr_t)d_carry & 7))
+    return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+  const double t0 = now_ms();
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  const u64 nt = (b.n + TILE - 1) / TILE;
+  if (int rc = c->d_colb.ensure(sidx_col_tile_bytes(nt ? nt : 1), res)) return rc;
+  const ColSlabIn sl{(const uint8_t *)b.d_data, b.n, b.end, b.front, b.base, file_size, first, last};
+  const int rc = column_slab_run(c, sl, (u32)column, c->d_colb, (ColCarry *)d_carry, (u64 *)d_rows, row_cap, c->stream, res);
+  res->total_ms = now_ms() - t0;
+  return rc;
+}
+
+// The slab walk over an open descriptor, whatever the node's size: the table back to a malloc'ed
+// array (result->path 5).
+int shockidx_column_fd_walk(shockidx_ctx *c, int fd, uint64_t n, int column, uint64_t slab_bytes, uint64_t halo_bytes,
+                            uint64_t **rows, shockidx_result *res) {
+  shockidx_result tmp;
+  if (!res) res = &tmp;
+  reset_result(res);
+  res->format = SHOCKIDX_FMT_LINE;
+  if (!c || !rows || fd < 0 || column < 1) return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+  *rows = nullptr;
+  TrimGuard trim{c};
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  TableSink sink(n / 64);  // (a row per cut, not per line: a table this size is rare)
+  if (!sink.out) return set_msg(res, SHOCKIDX_ENOMEM, "out of host memory");
+  if (int rc = column_fd_walk(c, fd, n, (u32)column, slab_bytes, halo_bytes, sink, res)) return rc;
+  *rows = (uint64_t *)sink.out;
+  sink.out = nullptr;
   return SHOCKIDX_OK;
 }
 

@@ -171,6 +171,28 @@ struct ColKey {
   u64 off, lo, len;
 };
 enum ColCtl : int { COL_BAD = 0, COL_NB, COL_B, COL_CTL_WORDS };
+// The column slab pass (shockidx_column_slab_device): the control words a slab adds -- the first
+// owned line it could not settle inside its window, its last non-blank owned line (start + 1, 0:
+// none) with that line's key span, and the rows it writes -- and the carry from slab to slab: what
+// column.go:64-101 knows at a slab's end (curr, the rows so far, whether a line was compared yet,
+// prev_str).  Two halves: a slab reads half `cur` and writes the other, then flips `cur`.
+constexpr u64 COL_KEYCAP = 64ull << 10;  // SHOCKIDX_COLUMN_KEYCAP: the longest key a carry holds
+enum ColSlabCtl : int { COLS_MORE = COL_CTL_WORDS, COLS_LAST, COLS_KLO, COLS_KLEN, COLS_ROWS, COL_SLAB_WORDS };
+static_assert(COL_SLAB_WORDS == 8, "the host reads the control words through 64 pinned bytes");
+struct ColCarryHalf {
+  u64 prev_cut, rows, seen, klen;
+  uint8_t key[COL_KEYCAP];
+};
+struct ColCarry {
+  u64 cur, pad[7];
+  ColCarryHalf half[2];
+};
+// what the slab kernels take besides the tile pass's arguments
+struct ColSlabArgs {
+  u64 end, base, file_size;  // readable bytes from data[0]; file offset of data[0]
+  const ColCarry *carry;
+  int eof, first, last;      // data[end) is the file's end; the slab starts / its owned bytes end the file
+};
 
 // Device result of finalize (mirrored by shockidx_result in include/shockidx.h).
 struct DevResult {

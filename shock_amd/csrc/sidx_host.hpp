@@ -293,6 +293,25 @@ struct FileSink : RowSink {  // the .idx temp file: rows are {u64 off, u64 len} 
   int fd = -1;
   int put(const uint8_t *src, sidx::u64 first, sidx::u64 nrows, Err res) override;
 };
+// ---- the column index in slabs (sidx_column_api.cpp, sidx_pipeline.cpp) ------------------------
+// One slab of the column slab pass: n owned bytes at d (16-byte aligned), `end` readable from d,
+// `front` before it, d[0] at file offset base.  ws: sidx_col_tile_bytes(tiles of n, at least 1)
+// bytes.  Returns like shockidx_column_slab_device; waits for the stream.
+struct ColSlabIn {
+  const uint8_t *d;
+  sidx::u64 n, end, front, base, file_size;
+  bool first, last;
+};
+int column_slab_run(shockidx_ctx *c, const ColSlabIn &sl, sidx::u32 column, void *ws, sidx::ColCarry *carry,
+                    sidx::u64 *d_rows, sidx::u64 row_cap, hipStream_t s, shockidx_result *res);
+// what the whole-node column build of an n-byte node holds at its peak: the node, its tile
+// workspace and its rows (DevBuf::ensure's growth included)
+sidx::u64 column_whole_bytes(sidx::u64 n);
+// The slab walk over the file's n bytes (S-byte slabs, 0: sized from the device budget; halo 0:
+// the default), rows to the sink slab by slab.  result->path 5.
+int column_fd_walk(shockidx_ctx *c, int fd, sidx::u64 n, sidx::u32 column, sidx::u64 S, sidx::u64 halo, RowSink &sink,
+                   shockidx_result *res);
+
 // *done = false: not applicable, the caller runs the plain path
 int build_host_pipelined(shockidx_ctx *c, const void *data, sidx::u64 n, int kind, int fmt, uint64_t **rows,
                          shockidx_result *res, bool *done);

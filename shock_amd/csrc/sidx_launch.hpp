@@ -90,6 +90,13 @@ hipError_t sidx_col_tile_rows(sidx::u64 n, void *ws, sidx::u64 count, sidx::u64 
     hipStream_t s);
 hipError_t sidx_col_check(const sidx::u64 *rows, sidx::u64 count, sidx::u64 n, sidx::DevResult *d_res,
     hipStream_t s);
+// the slab pass: one slab (n owned bytes at d, `front` readable before it) up to its host stop
+// (*ctl: the COL_SLAB_WORDS control words inside ws, sidx_col_tile_bytes of the slab's tiles);
+// then its nrows rows and the carry after it
+hipError_t sidx_col_slab_cuts(const uint8_t *d, sidx::u64 n, sidx::u64 front, const sidx::ColSlabArgs *sa,
+    sidx::u32 column, sidx::u32 grid, void *ws, const sidx::u64 **ctl, hipStream_t s);
+hipError_t sidx_col_slab_rows(const uint8_t *d, sidx::u64 n, const sidx::ColSlabArgs *sa, void *ws,
+    sidx::ColCarry *carry, sidx::u64 *rows, sidx::u64 nrows, hipStream_t s);
 hipError_t sidx_subset_compact(const sidx::u32 *keep, const sidx::u64 *rank, const sidx::i64 *val,
     const sidx::u32 *st, sidx::u64 m, sidx::i64 *cval, sidx::u32 *cst, sidx::u64 *cline, sidx::u64 *ctl,
     hipStream_t s);

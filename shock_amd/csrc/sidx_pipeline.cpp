@@ -51,6 +51,8 @@
 #include "../../include/shockidx.h"
 #include "sidx_common.hpp"
 #include "sidx_slabwalk.hpp"
+#include "sidx_colwalk.hpp"
+#include "sidx_launch.hpp"
 #include "sidx_host.hpp"
 
 using namespace sidx;
@@ -634,6 +636,152 @@ int build_fd_pipelined(shockidx_ctx *c, int fd, u64 n, int kind, int fmt, RowSin
     f = res->format == SHOCKIDX_FMT_LINE ? SHOCKIDX_FMT_AUTO : res->format;  // the format found at the file's start
     base = restart;
   }
+}
+
+// ---- the column index's walk -------------------------------------------------------------------
+// CreateColumnIndex (column.go:53-108) slab by slab through two slots: slab k + 1 is copied on the
+// copy stream (PageCacheSource: page-cache DMA, else the pinned staging, whose preads run on this
+// thread) while slab k's kernels run, each slab's rows go to the sink as they are made, and the
+// loop's state travels in the device carry.  sidx_colwalk.hpp holds the sizing and the one retry
+// rule.  The device holds the two slots, the carry with one slab's workspace (c->d_colb) and one
+// slab's rows, all exact-size.
+namespace {
+
+struct ColWalk {
+  shockidx_ctx *c;
+  u64 n, S, halo;
+  SlabEvents &events;
+  PageCacheSource &src;
+  Err res;
+  // slab p into slot i (its first byte at COLWALK_FRONT), its arrival recorded in events.ev[i]
+  int stage(int i, const ColSlabPos &p) {
+    if (int rc = src.copy_range(c->d_slot[i] + COLWALK_FRONT - p.front, p.lo - p.front, p.lo + p.end, p.lo - p.front)) return rc;
+    if (hipError_t e = hipEventRecord(events.ev[i], c->s_copy)) return set_hip(res, e, "event");
+    return 0;
+  }
+};
+
+// the slab's m rows (device rows [0, m)) through the pinned row buffers into the sink; *next: the
+// offset the table has reached (every row starts there: column.go:90-93)
+int col_rows_to_sink(shockidx_ctx *c, u64 m, ColRowCursor &cur, u64 *next, RowSink &sink, double *t_d2h,
+                     shockidx_result *res) {
+  const double td = now_ms();
+  const u64 per = STAGE_BYTES / 16;
+  int b = 0;
+  for (u64 done = 0; done < m; b ^= 1) {
+    const u64 k = m - done < per ? m - done : per;
+    HIPCHK(hipMemcpyAsync(c->h_rows[b], c->d_rows + 2 * done, k * 16, hipMemcpyDeviceToHost, c->stream), "rows copy");
+    HIPCHK(hipStreamSynchronize(c->stream), "rows copy");
+    const u64 *r = (const u64 *)c->h_rows[b];
+    for (u64 i = 0; i < k; ++i) {
+      if (r[2 * i] != *next) return set_msg(res, SHOCKIDX_EINTERNAL, SLAB_SEAM_MSG);
+      *next += r[2 * i + 1];
+    }
+    if (int rc = sink.put(c->h_rows[b], cur.take(k), k, res)) return rc;
+    done += k;
+  }
+  *t_d2h += now_ms() - td;
+  return 0;
+}
+
+}  // namespace
+
+int column_fd_walk(shockidx_ctx *c, int fd, u64 n, u32 column, u64 S, u64 halo, RowSink &sink, shockidx_result *res) {
+  const double t0 = now_ms();
+  res->path = 5;
+  res->format = SHOCKIDX_FMT_LINE;
+  if (!n) return SHOCKIDX_OK;  // one empty piece, blank: no rows (column.go:64-68,119)
+  const u64 budget = dev_budget(c);
+  const u64 carry_b = (sizeof(ColCarry) + 255) & ~255ull;
+  if (!halo) halo = colwalk_default_halo(budget);
+  if (halo > n) halo = n;
+  if (!S) {
+    S = colwalk_slab_bytes(budget, halo, carry_b, sidx_col_tile_bytes);
+    if (!S) return set_msg(res, SHOCKIDX_ENOMEM, "device memory: the column walk needs at least 32 MiB of its budget");
+  }
+  if (S > n) S = n;
+  hipStream_t s = c->stream;
+  if (!c->s_copy) HIPCHK(hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking), "copy stream");
+  for (int i = 0; i < 2; ++i)
+    if (!c->h_rows[i]) HIPCHK(hipHostMalloc(&c->h_rows[i], STAGE_BYTES, 0), "hipHostMalloc(rows)");
+  const u64 slot = colwalk_slot_bytes(S, halo), ws_b = sidx_col_tile_bytes((S + TILE - 1) / TILE);
+  u64 row_cap = colwalk_rows_cap(S);
+  if (c->d_slot[0].cap != slot || c->d_slot[1].cap != slot || c->d_colb.cap != carry_b + ws_b || c->d_rows.cap != row_cap) {
+    trim_workspace(c, 0);  // the caches of other builds go first
+    for (auto &sl : c->d_slot)
+      if (int rc = sl.exact(slot, res)) return rc;
+    if (int rc = c->d_colb.exact(carry_b + ws_b, res)) return rc;
+    if (int rc = c->d_rows.exact(row_cap, res)) return rc;
+  }
+  ColCarry *carry = c->d_colb.as<ColCarry>();
+  void *ws = c->d_colb + carry_b;
+  SlabEvents events(2, c->s_copy);  // (outlives the source's copies)
+  HIPCHK(events.create(), "event");
+  PageCacheSource src(c, fd, 0, n, res);
+  ColWalk w{c, n, S, halo, events, src, res};
+  ColRowCursor cur;
+  u64 next = 0;
+  double t_d2h = 0;
+  int i = 0;
+  ColSlabPos p = colwalk_slab_at(0, S, halo, n);
+  int rc = w.stage(0, p);
+  while (!rc) {
+    bool more = !p.last;
+    ColSlabPos q = p;
+    if (more) {  // the slab expected next, on its way while this one is indexed
+      q = colwalk_slab_at(p.lo + p.n, S, halo, n);
+      if ((rc = w.stage(i ^ 1, q))) break;
+    }
+    if (hipError_t e = hipStreamWaitEvent(s, events.ev[i], 0)) { rc = set_hip(res, e, "wait slab"); break; }
+    shockidx_result r2;
+    bool moved = false;
+    for (;;) {
+      reset_result(&r2);
+      const ColSlabIn in{c->d_slot[i] + COLWALK_FRONT, p.n, p.end, p.front, p.lo, n, p.first, p.last};
+      rc = column_slab_run(c, in, column, ws, carry, c->d_rows, row_cap, s, &r2);
+      res->kernel_ms += r2.kernel_ms;
+      if (rc == SHOCKIDX_ESPACE) {  // more cuts than a row per 32 bytes: the rows grow
+        row_cap = colwalk_grow_rows(row_cap, r2.count);
+        res->reruns++;
+        if ((rc = c->d_rows.exact(row_cap, res))) break;
+        continue;
+      }
+      if (rc == SHOCKIDX_EMORE) {  // the retry rule (sidx_colwalk.hpp)
+        u64 cut = 0;
+        if (colwalk_on_more(p.lo, r2.state_out, &cut) == ColRetry::NoMem) {
+          rc = set_msg(res, SHOCKIDX_ENOMEM, "device memory: a line or its key is longer than a slab slot can hold");
+          break;
+        }
+        p = colwalk_shorten(p, cut - p.lo, halo, n);
+        q = colwalk_slab_at(cut, S, halo, n);
+        more = moved = true;
+        res->reruns++;
+        continue;
+      }
+      if (rc) forward_error(res, r2, rc);
+      break;
+    }
+    if (rc) break;
+    if ((rc = col_rows_to_sink(c, r2.count, cur, &next, sink, &t_d2h, res))) break;
+    if (!more) break;
+    if (moved && (rc = w.stage(i ^ 1, q))) break;  // a fresh slot from where the shortened slab ends
+    p = q;
+    i ^= 1;
+  }
+  const hipError_t se = src.drain();  // before the pages are unpinned and unmapped
+  if (se != hipSuccess && rc >= 0 && rc != SHOCKIDX_EFORMAT) rc = set_hip(res, se, "H2D sync");
+  if (rc) {
+    res->count = 0;  // (column.go:76 returns count 0; an error leaves no table)
+    return rc;
+  }
+  if (cur.total && next != n) return set_msg(res, SHOCKIDX_EINTERNAL, SLAB_END_MSG);
+  res->count = cur.total;
+  res->index_ms = res->kernel_ms;
+  res->d2h_ms = t_d2h;
+  res->total_ms = now_ms() - t0;
+  res->h2d_ms = res->total_ms - t_d2h - res->kernel_ms;
+  res->status = SHOCKIDX_OK;
+  return SHOCKIDX_OK;
 }
 
 // Slab-pipelined FASTQ record build of a pinned host body: the body crosses PCIe in 1 GiB

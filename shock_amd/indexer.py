@@ -196,14 +196,14 @@ def CreateColumnIndex(c: ColumnIndexer, column: int, ofile: str):  # noqa: N802 
     written to ofile.  node/index.go:50-51 calls this directly: "column" is not in Indexers."""
     fd = c.f.fileno()
     size = os.fstat(fd).st_size
-    r = context().column_fd(fd, size, int(column))
+    tmpdir = os.path.join(PATH_DATA, "temp")
+    os.makedirs(tmpdir, exist_ok=True)
+    # shockidx_column_create: the whole-node build, or slab by slab within the context's device cap
+    r = context().column_create(fd, size, int(column), tmpdir, ofile)
     if r.status == L.EFORMAT:
         return 0, "array", ShockIndexError(r.err)
     if r.status != L.OK:
         raise L.ShockIdxError(r.status, (r.err or b"").decode("utf-8", "replace"))
-    tmpdir = os.path.join(PATH_DATA, "temp")
-    os.makedirs(tmpdir, exist_ok=True)
-    write_idx(r.rows if r.rows is not None else np.zeros((0, 2), np.uint64), tmpdir, ofile)
     return r.count, "array", None
 
 
