@@ -101,7 +101,9 @@ typedef struct shockidx_result {
                           3 slab-pipelined build (build_host of a pinned FASTQ body, build_fd / create),
                           4 the same through two slab slots within the context's device cap
                           (shockidx_ctx_set_dev_cap), 5 the column index in slabs
-                          (shockidx_column_slab_device, shockidx_column_fd_walk; a batch item: the batched walk) */
+                          (shockidx_column_slab_device, shockidx_column_fd_walk; a batch item: the batched walk),
+                          6 chunkrecord in slabs (shockidx_chunkrecord_slab_device, shockidx_chunkrecord_fd_walk,
+                          shockidx_chunkrecord_fd over the device cap); chunkrecord's whole-node build leaves 0 */
   uint32_t reruns;     /* builds re-run: a row-capacity overflow, a failed format speculation */
   double index_ms;     /* device time of the main index kernel alone (last pass) */
   uint64_t state_out;  /* format monoid state after the input (slab composition) */
@@ -475,6 +477,61 @@ int shockidx_chunkrecord_fd(shockidx_ctx *ctx, int fd, uint64_t n, int fmt, uint
  * d_rows receives result->count rows (16 * first row, 16 * rows): the "matrix" index. */
 int shockidx_chunkrecord_subset_device(shockidx_ctx *ctx, const void *d_ri, uint64_t nrows, void *d_rows,
                                        uint64_t row_cap, shockidx_result *result);
+
+/* ---- chunkrecord in slabs ---------------------------------------------------------------------
+ * The same table as shockidx_chunkrecord_device built slab by slab, so that the device holds two
+ * input slots, one slab's workspace and one slab's rows however large the node is.  SeekChunk
+ * (fastq.go:216-243, fasta.go:143-173) reads only 32 KiB windows and the file size, and a window's
+ * result depends on its own bytes alone, so a chunk is settled by any slab that holds the windows
+ * it evaluates.  What crosses a slab end is chunkrecord.go's loop state (curr and count,
+ * chunkrecord.go:54-55) and the recursion state of the one chunk left open: the offSet of
+ * SeekChunk's next window (== curr while the chunk's first window, the lastIndex one, has not been
+ * evaluated).  The carry holds them with the format and whether the EOF row (chunkrecord.go:60-64)
+ * is out.
+ *
+ * The slab (shockidx_slab): the window is the file bytes [base - front, base + end); d_data, the
+ * address of file byte base, is 16-byte aligned (base itself may be any offset); n and seq are
+ * ignored; is_first: the walk's first slab, whose window starts at 0 (front == base; a later slab's
+ * window may start at 0 too, with is_first 0); is_last: base + end == file_size.
+ * Slabs go in file order.  The first one initialises the carry (d_carry:
+ * shockidx_chunkrecord_carry_bytes() bytes of device memory, 8-byte aligned: a header and two
+ * halves, a slab reads one and writes the other) and resolves fmt: SHOCKIDX_FMT_AUTO needs the
+ * first min(32768, file_size) bytes inside the window and byte 0 at a 16-byte-aligned address, else
+ * SHOCKIDX_EINVAL; SAM is SHOCKIDX_EFORMAT as in shockidx_chunkrecord_device.  Later slabs take the
+ * format from the carry and ignore fmt.  chunk as in shockidx_chunkrecord_device, the same for
+ * every slab.
+ *
+ * A slab emits, at file offsets into d_rows[0 .. count), every row whose windows all lie in its
+ * window (chunkrecord.go:65-75), and on the last slab the EOF row.  A window [w, w + 32768) with
+ * w + 32768 > base + end is io.EOF on the last slab and "not here" on any other: the walk stops and
+ * the carry keeps (curr, offSet).  No byte outside the window is read.
+ *
+ * Returns: SHOCKIDX_OK, count = the rows written by this call -- possibly 0, when no window of the
+ * open chunk lies in the slab (e.g. chunk larger than the slab).  Any other return leaves the carry
+ * as it was (the first slab: as it initialised it) and no row that counts: SHOCKIDX_EINVAL, the
+ * carry's next window starts before the slab's window, or its walk has already ended;
+ * SHOCKIDX_ESPACE, count = the rows the slab needs.  The slabs' rows concatenated are
+ * shockidx_chunkrecord_device's table, and after the last slab the carry's count is the table's.
+ * Consecutive slabs never fail the carry's precondition when each window starts at most
+ * (32768 bytes) before the previous one's end.
+ * result->path 6; result->reruns = the speculative rounds of this slab (0 with
+ * SHOCKIDX_CHUNK_MODE=serial); result->state_out = 1 once the EOF row is out. */
+uint64_t shockidx_chunkrecord_carry_bytes(void);
+int shockidx_chunkrecord_slab_device(shockidx_ctx *ctx, const shockidx_slab *slab, uint64_t file_size, int fmt,
+                                     uint64_t chunk, void *d_carry, void *d_rows, uint64_t row_cap,
+                                     shockidx_result *result);
+/* The walk over an open descriptor (chunkrecord.go:41-99 whatever the node's size): slot k holds the
+ * file bytes [max(0, k S - 64 KiB), min(n, (k + 1) S)), slab k + 1 crosses PCIe into one slot while
+ * slab k is walked in the other, each slab's rows go to the host as they are made.  slab_bytes
+ * (S, at least 64 KiB) 0: sized so that the two slots, one slab's workspace and one slab's rows fit
+ * the context's device budget (shockidx_ctx_set_dev_cap; under 32 MiB: SHOCKIDX_ENOMEM).  No slab is
+ * submitted twice and no input needs a larger slot: the window a walk stops at always lies in the
+ * next slot.  *rows receives a malloc'ed table of result->count rows (free with shockidx_free);
+ * result->path 6, result->reruns = the speculative rounds of all slabs.  shockidx_chunkrecord_fd
+ * takes this walk when the whole-node build (the node, its FASTQ record table or FASTA tile arrays,
+ * the graph, the rows) does not fit the budget, and is otherwise unchanged. */
+int shockidx_chunkrecord_fd_walk(shockidx_ctx *ctx, int fd, uint64_t n, int fmt, uint64_t chunk, uint64_t slab_bytes,
+                                 uint64_t **rows, shockidx_result *result);
 
 /* ---- column index ------------------------------------------------------------------------
  * CreateColumnIndex (index/column.go:33-130, called from node/index.go:43-54 for

@@ -35,6 +35,7 @@ EXPORTS = ("shockidx_ctx_create", "shockidx_ctx_destroy", "shockidx_build_device
            "shockidx_comm_allgather", "shockidx_comm_destroy", "shockidx_comm_count", "shockidx_subset_index", "shockidx_subset_gather",
            "shockidx_subset_node",
            "shockidx_chunkrecord_device", "shockidx_chunkrecord_fd", "shockidx_chunkrecord_subset_device", "shockidx_create_subset_index",
+           "shockidx_chunkrecord_carry_bytes", "shockidx_chunkrecord_slab_device", "shockidx_chunkrecord_fd_walk",
            "shockidx_column_device", "shockidx_column_fd", "shockidx_column_carry_bytes", "shockidx_column_slab_device",
            "shockidx_column_fd_walk", "shockidx_column_create",
            "shockidx_idx_part", "shockidx_idx_range", "shockidx_filter_device", "shockidx_stream_filter_device", "shockidx_stream_last_stats",
@@ -147,6 +148,14 @@ def lib():
     L.shockidx_chunkrecord_fd.restype = i32
     L.shockidx_chunkrecord_subset_device.argtypes = [vp, vp, u64, vp, u64, PRes]
     L.shockidx_chunkrecord_subset_device.restype = i32
+    if hasattr(L, "shockidx_chunkrecord_slab_device") or not os.environ.get("SHOCKIDX_VARIANT"):
+        # (a variant library of older sources has none: tools/chunk_bench.py's parent arm)
+        L.shockidx_chunkrecord_carry_bytes.argtypes = []
+        L.shockidx_chunkrecord_carry_bytes.restype = u64
+        L.shockidx_chunkrecord_slab_device.argtypes = [vp, ctypes.POINTER(Slab), u64, i32, u64, vp, vp, u64, PRes]
+        L.shockidx_chunkrecord_slab_device.restype = i32
+        L.shockidx_chunkrecord_fd_walk.argtypes = [vp, i32, u64, i32, u64, u64, PPu64, PRes]
+        L.shockidx_chunkrecord_fd_walk.restype = i32
     L.shockidx_column_device.argtypes = [vp, vp, u64, i32, vp, u64, PRes]
     L.shockidx_column_device.restype = i32
     L.shockidx_column_fd.argtypes = [vp, i32, u64, i32, PPu64, PRes]

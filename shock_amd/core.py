@@ -302,6 +302,38 @@ class Context:
         """Rows a chunkrecord build can produce (include/shockidx.h)."""
         return n // ((chunk or 1048576) - 32767) + 2
 
+    # -- chunkrecord in slabs (shockidx_chunkrecord_slab_device and the walk over it) ------------
+    def chunkrecord_carry(self) -> "DeviceBuffer":
+        """Device memory for the carry of one chunkrecord slab walk (shockidx_chunkrecord_carry_bytes;
+        the first slab initialises it)."""
+        return self.alloc(int(self._lib.shockidx_chunkrecord_carry_bytes()))
+
+    def chunkrecord_slab(self, buf: "DeviceBuffer", base: int, front: int, end: int, file_size: int,
+                         carry: "DeviceBuffer", rows: "DeviceBuffer", fmt=None, chunk: int = 0, first=None,
+                         last=None) -> IndexResult:
+        """One slab of chunkrecord over the file bytes [base - front, base + end), where buf holds the
+        file from offset 0 (so base must be a multiple of 16).  Slabs go in file order with the carry
+        between them on the device.  OK: count rows at file offsets in rows (possibly 0); ESPACE: count
+        = the rows the slab needs; EINVAL: the carry's next window starts before the slab's window.
+        Anything but OK leaves the carry untouched.  first / last default to what the window says."""
+        slab = L.Slab(d_data=buf.ptr + base, n=end, end=end, front=front, base=base,
+                      is_first=int(front == base if first is None else first),
+                      is_last=int(base + end == file_size if last is None else last), seq=0, reserved=0)
+        res = L.Result()
+        rc = self._lib.shockidx_chunkrecord_slab_device(self._h, ctypes.byref(slab), file_size, _fmt(fmt), chunk,
+                                                        carry.ptr, rows.ptr, rows.nbytes // 16, ctypes.byref(res))
+        return _result(res, rc)
+
+    def chunkrecord_fd_walk(self, fd: int, size: int, fmt=None, chunk: int = 0, slab_bytes: int = 0) -> IndexResult:
+        """chunkRecord.Create over an open file, always slab by slab (shockidx_chunkrecord_fd_walk; 0:
+        slabs sized to the device budget); rows on the host, path 6."""
+        res = L.Result()
+        rows_p = ctypes.POINTER(ctypes.c_uint64)()
+        rc = self._lib.shockidx_chunkrecord_fd_walk(self._h, fd, size, _fmt(fmt), chunk, slab_bytes,
+                                                    ctypes.byref(rows_p), ctypes.byref(res))
+        rows = _take_rows(rows_p, int(res.count)) if rows_p else None
+        return _result(res, rc, rows)
+
     # -- column index (index/column.go:33-130) ---------------------------------------------------
     def column_device(self, d_data: int, n: int, column: int, d_rows: int, row_cap: int) -> IndexResult:
         """CreateColumnIndex over device memory: rows of the runs of the column-th tab-separated

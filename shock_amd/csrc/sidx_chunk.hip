@@ -36,6 +36,10 @@ namespace {
 typedef unsigned long long u64;
 typedef long long i64;
 typedef unsigned int u32;
+using sidx::ChunkView;
+using sidx::ChunkCarry;
+using sidx::ChunkCarryHalf;
+using namespace sidx::chunk_ctl;
 
 constexpr int WIN = 32768;
 constexpr int NT = 1024;
@@ -276,18 +280,23 @@ struct CrSmem {
 // Window [w, w + WIN) (fastq.go:222-241 / fasta.go:150-170): sm.found / sm.pos = the end of the
 // last (last != 0) or first Record match, or the '>' of the last / first "\n>" (then "\r>").
 // Uniform over the workgroup; ends with a barrier.
-__device__ __forceinline__ void eval_window(const uint8_t *__restrict__ d, u64 n, int fasta, u64 w, int last, CrSmem &sm) {
+// VIEW: d[x] is readable for x in [lo, n) only and d + lo is what is 16-byte aligned (a slab's
+// view, positions in file offsets): the aligned loads follow the address, and the 16 bytes below
+// an unaligned w are not touched when they start before lo.
+template <bool VIEW = false>
+__device__ __forceinline__ void eval_window(const uint8_t *__restrict__ d, u64 n, int fasta, u64 w, int last, CrSmem &sm,
+                                            u64 lo = 0) {
   const int t = threadIdx.x;
   // stage [w, w + WIN) in LDS, window byte j at raw[j]: two aligned 16-byte loads and a
   // funnel shift per 16 bytes (the shift is the same for every lane); FASTQ: the class words
   // from the same registers (16 bits per lane per class, a 16-bit LDS store each)
-  const u64 al0 = w & ~15ull;
-  const u32 sh = (u32)(w - al0);
+  const u32 sh = VIEW ? (u32)((uintptr_t)(d + w) & 15) : (u32)(w & 15);
+  const u64 al0 = w - sh;
   Masks &mk = sm.mk;
   for (int i = t; i < WIN / 16; i += NT) {
     const u64 al = al0 + 16ull * i;
     uint4 v;
-    if (al + 32 <= n) {
+    if (al + 32 <= n && (!VIEW || al >= lo)) {
       const uint4 *q = reinterpret_cast<const uint4 *>(d + al);
       v = cr_shift16(q[0], q[1], sh);
     } else {
@@ -402,13 +411,15 @@ __device__ __forceinline__ void eval_window(const uint8_t *__restrict__ d, u64 n
 // SeekChunk(curr, true) with its recursion into the following windows (fastq.go:216-243,
 // fasta.go:143-173): the chunk length m, or -1 when a window read is short (io.EOF).
 // Uniform over the workgroup.
-__device__ __forceinline__ i64 seek_step(const uint8_t *__restrict__ d, u64 n, int fasta, i64 chunk, i64 curr, CrSmem &sm) {
+template <bool VIEW = false>
+__device__ __forceinline__ i64 seek_step(const uint8_t *__restrict__ d, u64 n, int fasta, i64 chunk, i64 curr, CrSmem &sm,
+                                         u64 lo = 0) {
   i64 off = curr, acc = 0;
   int last = 1;
   for (;;) {
     const i64 w = off + chunk - WIN;
     if ((u64)w + WIN > n) return -1;
-    eval_window(d, n, fasta, (u64)w, last, sm);
+    eval_window<VIEW>(d, n, fasta, (u64)w, last, sm, lo);
     const int found = sm.found, pos = sm.pos;
     __syncthreads();  // every lane has read the result before the next window reuses sm
     if (found) return acc + chunk - WIN + pos;
@@ -464,16 +475,17 @@ constexpr int CT = 16384;                // position-table tile
 struct Bases {
   const u64 *p;   // ascending base positions, p[i * stride]
   u64 stride, count;
-  const u64 *ft;  // ft[t] = first base index with position >= t * CT, t in [0, ntile]
+  const u64 *ft;  // ft[t] = first base index with position >= org + t * CT, t in [0, ntile]
   u64 ntile;
+  u64 org;        // the position tile 0 starts at (0: the whole node; a slab's view: its first byte)
 };
 __device__ __forceinline__ u64 bpos(const Bases &b, u64 i) { return b.p[i * b.stride]; }
 // last base index with position <= y, -1 if none
 __device__ i64 last_le(const Bases &b, u64 y) {
-  u64 t = y / CT;
+  u64 t = y < b.org ? 0 : (y - b.org) / CT;
   if (t >= b.ntile) t = b.ntile - 1;
   u64 lo = b.ft[t], hi = b.ft[t + 1];
-  if (y >= (t + 1) * (u64)CT) { lo = hi; }  // past the last tile: every base <= y
+  if (y >= b.org + (t + 1) * (u64)CT) { lo = hi; }  // past the last tile: every base <= y
   while (lo < hi) {
     const u64 mid = (lo + hi) >> 1;
     if (bpos(b, mid) <= y) lo = mid + 1; else hi = mid;
@@ -496,7 +508,7 @@ __device__ u32 node_of(const Bases &b, int fasta, u64 y) {
 __global__ void k_cr_ftab(Bases b, u64 *__restrict__ ft) {
   const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (t > b.ntile) return;
-  const u64 y = t * (u64)CT;
+  const u64 y = b.org + t * (u64)CT;
   u64 lo = 0, hi = b.count;
   while (lo < hi) {
     const u64 mid = (lo + hi) >> 1;
@@ -648,6 +660,9 @@ __global__ void k_cr_path(Bases b, int fasta, u64 y, const u32 *__restrict__ JL,
 #define SIDX_CR_WPE 8  // waves per SIMD forced on k_cr_verify: two 1024-thread workgroups per CU (64 VGPRs, 9 spilled):
                        // FASTQ chunkrecord 8.16 -> 7.24 ms per 10 GiB; 0: the compiler's choice (89 VGPRs, one per CU)
 #endif
+// VIEW: (d, n) is a slab's view from file offset lo on (eval_window); a short window there is the
+// path's end whether or not the view is the file's last (the slab's walk closes the chunk).
+template <bool VIEW>
 #if SIDX_CR_WPE
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SIDX_CR_WPE, SIDX_CR_WPE))) void k_cr_verify(
 #else
@@ -655,12 +670,12 @@ __global__ __launch_bounds__(NT) void k_cr_verify(
 #endif
     const uint8_t *__restrict__ d, u64 n, int fasta, i64 chunk,
                                                   const u64 *__restrict__ pos, i64 *__restrict__ mres, u64 k0,
-                                                  u64 *__restrict__ ctl, u64 *__restrict__ rows, u64 row_cap) {
+                                                  u64 *__restrict__ ctl, u64 *__restrict__ rows, u64 row_cap, u64 lo) {
   __shared__ CrSmem sm;
   const u64 K = ctl[0];
   for (u64 k = blockIdx.x; k < K; k += gridDim.x) {
     const i64 p = (i64)pos[k];
-    const i64 m = seek_step(d, n, fasta, chunk, p, sm);
+    const i64 m = seek_step<VIEW>(d, n, fasta, chunk, p, sm, lo);
     if (threadIdx.x == 0) {
       mres[k] = m;
       if (k0 + k < row_cap) {
@@ -679,6 +694,131 @@ __global__ void k_cr_fin(const u64 *__restrict__ pos, const i64 *__restrict__ mr
     ctl[3] = (u64)mres[k];
     ctl[4] = pos[k] + (u64)mres[k];
   }
+}
+
+// ---- the slab step (shockidx_chunkrecord_slab_device) ----------------------------------------
+// SeekChunk reads only the windows [w, w + WIN) and the file size, and a window's result depends
+// on its own bytes alone, so a chunk is settled by any view that holds the windows it evaluates.
+// (d, n) below is a view's origin and readable end (positions are file offsets, n = hi): a window
+// that ends past n is io.EOF when the view is the file's last, and "not here" otherwise -- the walk
+// stops and the carry keeps (curr, off); off == curr means the chunk's first window is still to
+// come, so lastIndex (fastq.go:222) needs no word of its own.
+
+// seek_step resumed at window offSet `off` of the chunk that starts at curr: the chunk length, or
+// -1 with *stop = the offSet of the window that ends past n.  Uniform over the workgroup.
+__device__ __forceinline__ i64 seek_from(const uint8_t *__restrict__ d, u64 n, u64 lo, int fasta, i64 chunk, i64 curr,
+                                         i64 off, CrSmem &sm, i64 *stop) {
+  int last = off == curr;
+  for (;;) {
+    const i64 w = off + chunk - WIN;
+    if ((u64)w + WIN > n) { *stop = off; return -1; }
+    eval_window<true>(d, n, fasta, (u64)w, last, sm, lo);
+    const int found = sm.found, pos = sm.pos;
+    __syncthreads();  // every lane has read the result before the next window reuses sm
+    if (found) return (off - curr) + chunk - WIN + pos;
+    off += WIN;  // recursion: winSize + SeekChunk(offSet + winSize, false)
+    last = 0;
+  }
+}
+
+// The carry as the slab finds it, into the control words; the first slab writes it first.
+// CRS_BEFORE: the open chunk's next window starts before the view.
+__global__ void k_cr_slab_begin(ChunkView v, u64 chunk, int first, int fmt, ChunkCarry *__restrict__ carry,
+                                u64 *__restrict__ st) {
+  if (threadIdx.x) return;
+  if (first) {
+    carry->cur = 0;
+    ChunkCarryHalf &h0 = carry->half[0];
+    h0.curr = 0; h0.off = 0; h0.count = 0; h0.fmt = (u64)fmt; h0.done = 0;
+  }
+  const ChunkCarryHalf &h = carry->half[carry->cur & 1];
+  u64 status = CRS_OK;
+  if (h.done) status = CRS_ENDED;
+  else if (h.off + chunk - WIN < v.lo) status = CRS_BEFORE;
+  st[CRS_STATUS] = status;
+  st[CRS_FMT] = h.fmt;
+  st[CRS_CURR] = h.curr;
+  st[CRS_OFF] = h.off;
+  st[CRS_COUNT] = h.count;
+  st[CRS_DONE] = 0;
+  st[CRS_ROWS] = 0;
+  st[CRS_STOP] = 0;
+}
+
+// The serial walk over a view (chunkrecord.go:54-97 from the state in st, or from the start y of a
+// chunk with k rows of this slab out): rows at file offsets, until a window is not in the view or
+// the EOF row is out (CRS_STOP), or max_steps chunks.
+__global__ __launch_bounds__(NT) void k_cr_slab_walk(const uint8_t *__restrict__ d, u64 n, u64 lo, u64 size, int vlast, int fasta,
+                                                     i64 chunk, u64 *__restrict__ st, u64 *__restrict__ rows,
+                                                     u64 row_cap, u64 max_steps, int from_args, u64 y, u64 k) {
+  __shared__ CrSmem sm;
+  i64 curr = from_args ? (i64)y : (i64)st[CRS_CURR];
+  i64 off = from_args ? (i64)y : (i64)st[CRS_OFF];
+  u64 cnt = from_args ? k : st[CRS_ROWS];
+  int done = 0, stop = 0;
+  __syncthreads();  // every lane holds the state before lane 0 writes it back
+  for (u64 step = 0; step < max_steps; ++step) {
+    i64 at = off;
+    const i64 m = seek_from(d, n, lo, fasta, chunk, curr, off, sm, &at);
+    if (m < 0) {
+      stop = 1;
+      if (vlast) {  // io.EOF: the final row (chunkrecord.go:60-64)
+        if (threadIdx.x == 0 && cnt < row_cap) { rows[2 * cnt] = (u64)curr; rows[2 * cnt + 1] = size - (u64)curr; }
+        cnt++;
+        done = 1;
+      } else {
+        off = at;
+      }
+      break;
+    }
+    if (threadIdx.x == 0 && cnt < row_cap) { rows[2 * cnt] = (u64)curr; rows[2 * cnt + 1] = (u64)m; }
+    cnt++;
+    curr += m;
+    off = curr;
+  }
+  if (threadIdx.x == 0) {
+    st[CRS_CURR] = (u64)curr;
+    st[CRS_OFF] = (u64)off;
+    st[CRS_ROWS] = cnt;
+    st[CRS_DONE] = (u64)done;
+    st[CRS_STOP] = (u64)stop;
+  }
+}
+
+// The slab's end state into the carry's other half, then the flip (launched only for a slab that
+// succeeded): one lane, plain stores.
+__global__ void k_cr_slab_commit(ChunkCarry *__restrict__ carry, const u64 *__restrict__ st) {
+  if (threadIdx.x) return;
+  const u64 cur = carry->cur & 1;
+  ChunkCarryHalf &o = carry->half[cur ^ 1];
+  o.curr = st[CRS_CURR];
+  o.off = st[CRS_OFF];
+  o.count = st[CRS_COUNT] + st[CRS_ROWS];
+  o.fmt = st[CRS_FMT];
+  o.done = st[CRS_DONE];
+  __threadfence();
+  carry->cur = cur ^ 1;
+}
+
+// k_cr_fin for a view: ctl[3] = the exact m of the chunk the round ends at (the first bad one, or
+// the path's last when the whole path holds: its window is short, m < 0), ctl[4] = where the walk
+// goes on -- that chunk's start when m < 0 (it stays open), else its end.
+__global__ void k_cr_slab_fin(const u64 *__restrict__ pos, const i64 *__restrict__ mres, u64 *__restrict__ ctl) {
+  u64 k = ctl[2];
+  if (k == ~0ull) {
+    if (!ctl[0]) return;
+    k = ctl[0] - 1;
+  }
+  const i64 m = mres[k];
+  ctl[3] = (u64)m;
+  ctl[4] = m < 0 ? pos[k] : pos[k] + (u64)m;
+}
+
+__global__ void k_cr_slab_nodes(u64 *__restrict__ G, u64 count, u64 stride, u64 bias, u64 curr) {
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const u64 g = G[i * stride] + bias;
+  G[i * stride] = (i == 0 || g < curr) ? curr : g;
 }
 
 // FASTA node positions: per CT tile the "\n>" pairs whose '>' lies in it (pass 1 counts, pass
@@ -807,12 +947,13 @@ extern "C" hipError_t sidx_cr_gpos_write(const uint8_t *d, u64 n, const u64 *tcn
 extern "C" u32 sidx_cr_gslot() { return GSLOT; }
 
 // Predicted-successor graph over the nodes and its L = 2^levels jump table: ft ((ntile + 1)
-// words), J1 / Ja / Jb (nodes words each).  *JL receives the L-step table.
+// words, ntile = (n - org) / CT + 1), J1 / Ja / Jb (nodes words each).  *JL receives the L-step
+// table.  org: where the position tiles start (0 for a whole node).
 extern "C" hipError_t sidx_cr_graph(const uint8_t *d, u64 n, int fasta, u64 chunk, const u64 *base, u64 stride,
-                                    u64 count, u64 *ft, u32 *J1, u32 *Ja, u32 *Jb, int levels, const u32 **JL,
+                                    u64 count, u64 org, u64 *ft, u32 *J1, u32 *Ja, u32 *Jb, int levels, const u32 **JL,
                                     hipStream_t s) {
-  const u64 ntile = n / CT + 1;
-  Bases b{base, stride, count, ft, ntile};
+  const u64 ntile = (n - org) / CT + 1;
+  Bases b{base, stride, count, ft, ntile, org};
   hipLaunchKernelGGL(k_cr_ftab, dim3((u32)((ntile + 256) / 256)), dim3(256), 0, s, b, ft);
   const u64 nn = fasta ? count : 3 * count;
   const u32 g = (u32)((nn + 255) / 256);
@@ -830,21 +971,61 @@ extern "C" hipError_t sidx_cr_graph(const uint8_t *d, u64 n, int fasta, u64 chun
 
 // One round: the path from position y (at most cap nodes; its first chunk is row k0), every
 // chunk of it evaluated exactly (verify_grid workgroups), the first disagreement into ctl[2..4].
+// slab: the round of a slab's view (k_cr_slab_fin closes it: ctl[3..4] also when the whole path holds).
 extern "C" hipError_t sidx_cr_round(const uint8_t *d, u64 n, int fasta, u64 chunk, const u64 *base, u64 stride,
-                                    u64 count, const u64 *ft, const u32 *JL, const u32 *J1, u32 L, u64 y, u64 k0,
-                                    u64 cap, u32 *heads, u64 *pos, i64 *mres, u64 *ctl, u64 *rows, u64 row_cap,
-                                    u32 verify_grid, hipStream_t s) {
-  Bases b{base, stride, count, ft, n / CT + 1};
+                                    u64 count, u64 org, const u64 *ft, const u32 *JL, const u32 *J1, u32 L, u64 y,
+                                    u64 k0, u64 cap, u32 *heads, u64 *pos, i64 *mres, u64 *ctl, u64 *rows,
+                                    u64 row_cap, u32 verify_grid, int slab, hipStream_t s) {
+  Bases b{base, stride, count, ft, (n - org) / CT + 1, org};
   hipLaunchKernelGGL(k_cr_path, dim3(1), dim3(256), 0, s, b, fasta, y, JL, J1, L, cap, heads, pos, ctl);
-  hipLaunchKernelGGL(k_cr_verify, dim3(verify_grid), dim3(NT), 0, s, d, n, fasta, (i64)chunk, pos, mres, k0, ctl,
-                     rows, row_cap);
-  hipLaunchKernelGGL(k_cr_fin, dim3(1), dim3(1), 0, s, pos, mres, ctl);
+  if (slab) {  // (org: the view's first byte)
+    hipLaunchKernelGGL(k_cr_verify<true>, dim3(verify_grid), dim3(NT), 0, s, d, n, fasta, (i64)chunk, pos, mres, k0, ctl,
+                       rows, row_cap, org);
+    hipLaunchKernelGGL(k_cr_slab_fin, dim3(1), dim3(1), 0, s, pos, mres, ctl);
+  } else {
+    hipLaunchKernelGGL(k_cr_verify<false>, dim3(verify_grid), dim3(NT), 0, s, d, n, fasta, (i64)chunk, pos, mres, k0,
+                       ctl, rows, row_cap, 0ull);
+    hipLaunchKernelGGL(k_cr_fin, dim3(1), dim3(1), 0, s, pos, mres, ctl);
+  }
+  return hipGetLastError();
+}
+
+// ---- the slab step's launchers ---------------------------------------------------------------
+// The evaluators above take (d, n) with positions counted from d[0] and n both the readable end
+// and the file's end.  A view goes through them as (v.d - v.lo, v.hi): positions are file offsets,
+// no window below v.lo is ever asked for (the carry's precondition, checked by k_cr_slab_begin), no
+// byte below v.lo or past v.hi is read (eval_window<true>); what "short window" means -- io.EOF or
+// "not here" -- is decided by the slab kernels from v.last.
+static const uint8_t *view_origin(const ChunkView &v) { return v.d - v.lo; }
+
+extern "C" hipError_t sidx_cr_slab_begin(const ChunkView *v, u64 chunk, int first, int fmt, ChunkCarry *carry, u64 *st,
+                                         hipStream_t s) {
+  hipLaunchKernelGGL(k_cr_slab_begin, dim3(1), dim3(64), 0, s, *v, chunk, first, fmt, carry, st);
+  return hipGetLastError();
+}
+// the serial walk over the view from the state in st (from_args: from chunk start y with k rows of
+// this slab out), at most max_steps chunks
+extern "C" hipError_t sidx_cr_slab_walk(const ChunkView *v, int fasta, u64 chunk, u64 *st, u64 *rows, u64 row_cap,
+                                        u64 max_steps, int from_args, u64 y, u64 k, hipStream_t s) {
+  hipLaunchKernelGGL(k_cr_slab_walk, dim3(1), dim3(NT), 0, s, view_origin(*v), v->hi, v->lo, v->size, v->last, fasta,
+                     (i64)chunk, st, rows, row_cap, max_steps, from_args, y, k);
+  return hipGetLastError();
+}
+extern "C" hipError_t sidx_cr_slab_commit(ChunkCarry *carry, const u64 *st, hipStream_t s) {
+  hipLaunchKernelGGL(k_cr_slab_commit, dim3(1), dim3(64), 0, s, carry, st);
+  return hipGetLastError();
+}
+// the view's node positions brought to file offsets behind node 0 = curr: G[0] = curr, G[i] =
+// max(G[i] + bias, curr) (FASTA: the "\n>" positions of the view counted from its scan start); or
+// row 0 of a record table = (curr, 0) (FASTQ: the view's record index from row 1 on)
+extern "C" hipError_t sidx_cr_slab_nodes(u64 *G, u64 count, u64 stride, u64 bias, u64 curr, hipStream_t s) {
+  hipLaunchKernelGGL(k_cr_slab_nodes, dim3((u32)((count + 255) / 256)), dim3(256), 0, s, G, count, stride, bias, curr);
   return hipGetLastError();
 }
 
 extern "C" int sidx_cr_verify_blocks_per_cu() {
   int nb = 0;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_cr_verify, NT, 0) == hipSuccess ? nb : 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_cr_verify<false>, NT, 0) == hipSuccess ? nb : 0;
 }
 
 namespace {

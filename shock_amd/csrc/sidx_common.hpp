@@ -194,6 +194,35 @@ struct ColSlabArgs {
   int eof, first, last;      // data[end) is the file's end; the slab starts / its owned bytes end the file
 };
 
+// The chunkrecord slab step (shockidx_chunkrecord_slab_device).  The view: file bytes [lo, hi) at a
+// 16-byte-aligned device address, the file's size, and whether hi is the file's end.  The carry:
+// chunkrecord.go:54-55's loop state (curr, count) and the recursion state of the one chunk a slab
+// end can leave open -- off, the offSet of SeekChunk's next window (fastq.go:216-243), == curr
+// while the chunk's first window (the lastIndex one) has not been evaluated -- with the format the
+// first slab resolved and whether the EOF row is out.  Two halves: a slab reads half `cur` and
+// writes the other, then flips `cur`; a slab that fails writes neither.
+struct ChunkView {
+  const uint8_t *d;  // file byte lo
+  u64 lo, hi, size;
+  int last;          // hi == size
+};
+struct ChunkCarryHalf {
+  u64 curr, off, count, fmt, done, pad[3];
+};
+struct ChunkCarry {
+  u64 cur, pad[7];
+  ChunkCarryHalf half[2];
+};
+// the slab step's control words: what the carry held when the slab began (CRS_STATUS: 0, or why the
+// slab cannot run), then the state the walk kernels advance -- CRS_ROWS rows of this slab so far,
+// CRS_STOP: the open chunk's next window is not in the view (or the EOF row is out: CRS_DONE)
+namespace chunk_ctl {  // (a namespace of their own: sidx_chunk.hip imports these names alone)
+enum ChunkSlabCtl : int { CRS_STATUS = 0, CRS_FMT, CRS_CURR, CRS_OFF, CRS_COUNT, CRS_DONE, CRS_ROWS, CRS_STOP, CRS_WORDS };
+enum ChunkSlabStatus : int { CRS_OK = 0, CRS_BEFORE = 1, CRS_ENDED = 2 };
+}  // namespace chunk_ctl
+using namespace chunk_ctl;
+static_assert(CRS_WORDS == 8, "the host reads the control words through 64 pinned bytes");
+
 // Device result of finalize (mirrored by shockidx_result in include/shockidx.h).
 struct DevResult {
   u64 count;       // records (rows) produced, Go's `count`

@@ -20,6 +20,10 @@
 #include "sidx_common.hpp"
 #include "sidx_devbuf.hpp"
 
+namespace sidx {
+struct ChunkWalkDev;  // sidx_chunkwalk.hpp
+}
+
 namespace sidx_host {
 
 constexpr size_t STAGE_BYTES = 64ull << 20;  // pinned staging chunk
@@ -116,6 +120,7 @@ struct shockidx_ctx {
   Buf<u32> d_tile_words{bufs};     //   per-tile results (FQ_TILE_WORDS per tile)
   Buf<uint8_t> d_cra{bufs};        // speculative chunkrecord: FASTQ record table / FASTA tile counts (bytes)
   Buf<uint8_t> d_crb{bufs};        //   node positions, jump tables, path, results (bytes)
+  Buf<uint8_t> d_crc{bufs};        //   the slab walk's carry (bytes)
   // fd builds within the device cap: the two slab slots (exact-size, bytes each)
   Buf<uint8_t> d_slot[2] = {Buf<uint8_t>{bufs, BufClass::Large, true, "hipMalloc(slab slot)"},
                             Buf<uint8_t>{bufs, BufClass::Large, true, "hipMalloc(slab slot)"}};
@@ -311,6 +316,22 @@ sidx::u64 column_whole_bytes(sidx::u64 n);
 // the default), rows to the sink slab by slab.  result->path 5.
 int column_fd_walk(shockidx_ctx *c, int fd, sidx::u64 n, sidx::u32 column, sidx::u64 S, sidx::u64 halo, RowSink &sink,
                    shockidx_result *res);
+
+// ---- the chunkrecord index in slabs (sidx_chunk_api.cpp, sidx_pipeline.cpp) --------------------
+// One slab of chunkrecord over the view v (sidx_common.hpp) with the carry on the device; first:
+// the carry is initialised with fmt (later slabs take the format from it).  Rows at file offsets
+// into rows[0..row_cap).  Returns like shockidx_chunkrecord_slab_device; waits for the stream.
+int chunk_slab_run(shockidx_ctx *c, const sidx::ChunkView &v, sidx::u64 chunk, bool first, int fmt,
+                   sidx::ChunkCarry *carry, sidx::u64 *rows, sidx::u64 row_cap, hipStream_t s, shockidx_result *res);
+// what the whole-node chunkrecord build of an n-byte node holds at its peak (the node, its FASTQ
+// record table or FASTA tile arrays, the graph, the rows), next to one_pass_bytes
+sidx::u64 chunk_one_pass_bytes(shockidx_ctx *c, sidx::u64 n, sidx::u64 chunk);
+// the device-side figures the walk's sizing takes (sidx_chunkwalk.hpp) for views of len bytes
+sidx::ChunkWalkDev chunk_walk_dev(shockidx_ctx *c, sidx::u64 len);
+// The slab walk over the file's n bytes (S-byte slabs, 0: sized from the device budget), rows to
+// the sink slab by slab.  result->path 6.
+int chunk_fd_walk(shockidx_ctx *c, int fd, sidx::u64 n, int fmt, sidx::u64 chunk, sidx::u64 S, RowSink &sink,
+                  shockidx_result *res);
 
 // *done = false: not applicable, the caller runs the plain path
 int build_host_pipelined(shockidx_ctx *c, const void *data, sidx::u64 n, int kind, int fmt, uint64_t **rows,

@@ -30,13 +30,24 @@ hipError_t sidx_cr_gpos_write(const uint8_t *d, sidx::u64 n, const sidx::u64 *tc
     const uint16_t *slot, sidx::u64 *G, hipStream_t s);
 sidx::u32 sidx_cr_gslot();
 hipError_t sidx_cr_graph(const uint8_t *d, sidx::u64 n, int fasta, sidx::u64 chunk, const sidx::u64 *base,
-    sidx::u64 stride, sidx::u64 count, sidx::u64 *ft, sidx::u32 *J1, sidx::u32 *Ja, sidx::u32 *Jb, int levels,
-    const sidx::u32 **JL, hipStream_t s);
+    sidx::u64 stride, sidx::u64 count, sidx::u64 org, sidx::u64 *ft, sidx::u32 *J1, sidx::u32 *Ja, sidx::u32 *Jb,
+    int levels, const sidx::u32 **JL, hipStream_t s);
 hipError_t sidx_cr_round(const uint8_t *d, sidx::u64 n, int fasta, sidx::u64 chunk, const sidx::u64 *base,
-    sidx::u64 stride, sidx::u64 count, const sidx::u64 *ft, const sidx::u32 *JL, const sidx::u32 *J1, sidx::u32 L,
-    sidx::u64 y, sidx::u64 k0, sidx::u64 cap, sidx::u32 *heads, sidx::u64 *pos, sidx::i64 *mres, sidx::u64 *ctl,
-    sidx::u64 *rows, sidx::u64 row_cap, sidx::u32 verify_grid, hipStream_t s);
+    sidx::u64 stride, sidx::u64 count, sidx::u64 org, const sidx::u64 *ft, const sidx::u32 *JL, const sidx::u32 *J1,
+    sidx::u32 L, sidx::u64 y, sidx::u64 k0, sidx::u64 cap, sidx::u32 *heads, sidx::u64 *pos, sidx::i64 *mres,
+    sidx::u64 *ctl, sidx::u64 *rows, sidx::u64 row_cap, sidx::u32 verify_grid, int slab, hipStream_t s);
 int sidx_cr_verify_blocks_per_cu();
+// the chunkrecord slab step (sidx_chunk.hip; the view, the carry and the control words st:
+// sidx_common.hpp): the carry into st (the first slab initialises it with fmt); the serial walk over
+// the view from st, or from chunk start y with k rows out; the end state into the carry; node 0 of
+// a view's position table
+hipError_t sidx_cr_slab_begin(const sidx::ChunkView *v, sidx::u64 chunk, int first, int fmt, sidx::ChunkCarry *carry,
+    sidx::u64 *st, hipStream_t s);
+hipError_t sidx_cr_slab_walk(const sidx::ChunkView *v, int fasta, sidx::u64 chunk, sidx::u64 *st, sidx::u64 *rows,
+    sidx::u64 row_cap, sidx::u64 max_steps, int from_args, sidx::u64 y, sidx::u64 k, hipStream_t s);
+hipError_t sidx_cr_slab_commit(sidx::ChunkCarry *carry, const sidx::u64 *st, hipStream_t s);
+hipError_t sidx_cr_slab_nodes(sidx::u64 *G, sidx::u64 count, sidx::u64 stride, sidx::u64 bias, sidx::u64 curr,
+    hipStream_t s);
 sidx::u32 sidx_fa_slot();
 hipError_t sidx_fa_bnd_count(const uint8_t *d, sidx::u64 n, sidx::u64 *lnl, sidx::u64 *lgt, sidx::u64 *cnl,
     sidx::u64 *cgt, sidx::u64 *tcnt, sidx::u64 *toff, uint16_t *slot, void *tmp, size_t *tmp_bytes, hipStream_t s);

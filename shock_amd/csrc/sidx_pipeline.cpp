@@ -52,6 +52,7 @@
 #include "sidx_common.hpp"
 #include "sidx_slabwalk.hpp"
 #include "sidx_colwalk.hpp"
+#include "sidx_chunkwalk.hpp"
 #include "sidx_launch.hpp"
 #include "sidx_host.hpp"
 
@@ -775,6 +776,98 @@ int column_fd_walk(shockidx_ctx *c, int fd, u64 n, u32 column, u64 S, u64 halo, 
     return rc;
   }
   if (cur.total && next != n) return set_msg(res, SHOCKIDX_EINTERNAL, SLAB_END_MSG);
+  res->count = cur.total;
+  res->index_ms = res->kernel_ms;
+  res->d2h_ms = t_d2h;
+  res->total_ms = now_ms() - t0;
+  res->h2d_ms = res->total_ms - t_d2h - res->kernel_ms;
+  res->status = SHOCKIDX_OK;
+  return SHOCKIDX_OK;
+}
+
+// ---- the chunkrecord index's walk --------------------------------------------------------------
+// chunkRecord.Create (chunkrecord.go:41-99) slab by slab through two slots: slot k holds file bytes
+// [max(0, k S - H), min(n, (k + 1) S)) from its first byte on, slab k + 1 is copied on the copy
+// stream while slab k is walked, each slab's rows go to the sink as they are made, and the loop's
+// state travels in the device carry.  sidx_chunkwalk.hpp holds the layout, the sizing and the reason
+// no slab is ever submitted twice.  The device holds the two slots, the carry, one slab's
+// workspace (c->d_cra, c->d_crb and, for FASTQ, the tile block of the view's record index) and one
+// slab's rows.
+int chunk_fd_walk(shockidx_ctx *c, int fd, u64 n, int fmt, u64 chunk, u64 S, RowSink &sink, shockidx_result *res) {
+  const double t0 = now_ms();
+  res->path = 6;
+  hipStream_t s = c->stream;
+  if (!S) {
+    const u64 top = n < CHUNKWALK_MAX_SLAB ? n : CHUNKWALK_MAX_SLAB;
+    S = chunkwalk_slab_bytes(dev_budget(c), chunk, chunk_walk_dev(c, top + CHUNKWALK_HALO));
+    if (!S) return set_msg(res, SHOCKIDX_ENOMEM, "device memory: the chunkrecord walk needs at least 32 MiB of its budget");
+  }
+  if (S > n) S = n ? n : 1;
+  const u64 vmax = S + CHUNKWALK_HALO;
+  const ChunkWalkDev dv = chunk_walk_dev(c, vmax);
+  if (!c->s_copy) HIPCHK(hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking), "copy stream");
+  for (int i = 0; i < 2; ++i)
+    if (!c->h_rows[i]) HIPCHK(hipHostMalloc(&c->h_rows[i], STAGE_BYTES, 0), "hipHostMalloc(rows)");
+  const u64 slot = chunkwalk_slot_bytes(S), cra = chunkwalk_cra_bytes(vmax, dv.scan_bytes, dv.gslot),
+            crb = chunkwalk_crb_bytes(vmax, chunk), row_cap = chunkwalk_row_bound(vmax, chunk);
+  if (c->d_slot[0].cap != slot || c->d_slot[1].cap != slot || c->d_cra.cap != cra || c->d_crb.cap != crb ||
+      c->d_crc.cap != dv.carry_bytes || c->d_rows.cap != row_cap) {
+    trim_workspace(c, 0);  // the caches of other builds go first
+    for (auto &sl : c->d_slot)
+      if (int rc = sl.exact(slot, res)) return rc;
+    if (int rc = c->d_cra.exact(cra, res)) return rc;
+    if (int rc = c->d_crb.exact(crb, res)) return rc;
+    if (int rc = c->d_crc.exact(dv.carry_bytes, res)) return rc;
+    if (int rc = c->d_rows.exact(row_cap, res)) return rc;
+  }
+  ChunkCarry *carry = c->d_crc.as<ChunkCarry>();
+  SlabEvents events(2, c->s_copy);  // (outlives the source's copies)
+  HIPCHK(events.create(), "event");
+  PageCacheSource src(c, fd, 0, n, res);
+  auto stage = [&](u64 k) -> int {  // slab k into slot k mod 2, its arrival recorded in that slot's event
+    const ChunkSlot p = chunkwalk_slot(k, S, n);
+    if (p.hi > p.lo)
+      if (int rc = src.copy_range(c->d_slot[k & 1], p.lo, p.hi, p.lo)) return rc;
+    if (hipError_t e = hipEventRecord(events.ev[k & 1], c->s_copy)) return set_hip(res, e, "event");
+    return 0;
+  };
+  const u64 K = chunkwalk_slots(S, n);
+  ColRowCursor cur;
+  u64 next = 0;
+  double t_d2h = 0;
+  int kfmt = 0;
+  int rc = stage(0);
+  for (u64 k = 0; !rc && k < K; ++k) {
+    if (k + 1 < K && (rc = stage(k + 1))) break;  // the next slab, on its way while this one is walked
+    if (hipError_t e = hipStreamWaitEvent(s, events.ev[k & 1], 0)) { rc = set_hip(res, e, "wait slab"); break; }
+    const ChunkSlot p = chunkwalk_slot(k, S, n);
+    const ChunkView v{c->d_slot[k & 1], p.lo, p.hi, n, p.last};
+    if (k == 0) {  // the first slab resolves the format (S >= 64 KiB: it holds the bytes detection reads)
+      if ((rc = resolve_format(c, v.d, v.hi, SHOCKIDX_RECORD, fmt, s, &kfmt, res))) break;
+      res->format = kfmt;
+      if (kfmt == SHOCKIDX_FMT_SAM) {
+        rc = set_msg(res, SHOCKIDX_EFORMAT, "chunkrecord: sam.SeekChunk never advances (reference loops forever)");
+        break;
+      }
+      if (kfmt != SHOCKIDX_FMT_FASTA && kfmt != SHOCKIDX_FMT_FASTQ) { rc = set_msg(res, SHOCKIDX_EINVAL, "invalid format"); break; }
+    }
+    shockidx_result r2;
+    reset_result(&r2);
+    rc = chunk_slab_run(c, v, chunk, k == 0, kfmt, carry, c->d_rows, row_cap, s, &r2);
+    res->kernel_ms += r2.kernel_ms;
+    res->reruns += r2.reruns;
+    if (rc == SHOCKIDX_ESPACE) rc = set_msg(res, SHOCKIDX_EINTERNAL, "internal error: a slab's rows exceed their bound");
+    else if (rc) forward_error(res, r2, rc);
+    if (rc) break;
+    rc = col_rows_to_sink(c, r2.count, cur, &next, sink, &t_d2h, res);
+  }
+  const hipError_t se = src.drain();  // before the pages are unpinned and unmapped
+  if (se != hipSuccess && rc >= 0 && rc != SHOCKIDX_EFORMAT) rc = set_hip(res, se, "H2D sync");
+  if (rc) {
+    res->count = 0;
+    return rc;
+  }
+  if (next != n) return set_msg(res, SHOCKIDX_EINTERNAL, SLAB_END_MSG);
   res->count = cur.total;
   res->index_ms = res->kernel_ms;
   res->d2h_ms = t_d2h;

@@ -77,7 +77,9 @@ class LineIndexer(_GPUIndexer):
 
 class ChunkRecordIndexer(_GPUIndexer):
     """chunkRecord.Create (index/chunkrecord.go:41-228).  Non-subset nodes (:41-99): the file goes
-    to HBM and shockidx_chunkrecord_fd builds the table.  Subset nodes (:100-228): the subset
+    to HBM and shockidx_chunkrecord_fd builds the table -- whole when that fits the context's device
+    cap (Context.set_dev_cap), else slab by slab through two slots (result.path 6).  Subset nodes
+    (:100-228): the subset
     node's record index file (sn_index_path) is read whole rows at a time and its rows are
     grouped on the device (shockidx_chunkrecord_subset_device) into the "matrix" index.  Either
     way write_idx renames the table into place."""
