@@ -26,6 +26,8 @@
  *   shockidx_column_device / shockidx_column_fd  CreateColumnIndex: index/column.go:33-130
  *   shockidx_column_slab_device / shockidx_column_fd_walk  the same loop (column.go:53-108) slab by slab
  *   shockidx_column_create  CreateColumnIndex with its temp file and rename (column.go:34-40,127)
+ *   shockidx_subset_slab_device / shockidx_subset_fd_walk / shockidx_subset_create  the subset builders
+ *       (index/subset.go:36-303) slab by slab and with their file protocol
  *   shockidx_download_plan the section list of a ?download&index=X&part=a&part=b... request, the
  *                          s.R = append(...) loops of controller/node/single.go:372-483 (Idx.Part /
  *                          Idx.Range per part, the subset node's chunkrecord branch :401-425) and
@@ -54,7 +56,9 @@ extern "C" {
  *    shockidx_stream_last_stats, shockidx_build_batch_device, shockidx_build_batch_host,
  *    shockidx_batch_error, shockidx_batch_last_stats, shockidx_column_carry_bytes,
  *    shockidx_column_slab_device, shockidx_column_fd_walk, shockidx_column_create (and the code
- *    SHOCKIDX_EMORE, which only shockidx_column_slab_device returns) */
+ *    SHOCKIDX_EMORE, which only shockidx_column_slab_device returns), shockidx_subset_carry_bytes,
+ *    shockidx_subset_slab_device, shockidx_subset_fd_walk, shockidx_subset_create,
+ *    shockidx_subset_last_stats */
 #define SHOCKIDX_ABI_VERSION 5
 
 /* index kinds = the registry keys served (index/index.go:21-28) */
@@ -337,6 +341,112 @@ int shockidx_subset_node(shockidx_ctx *ctx, const void *d_ids, uint64_t ids_len,
 int shockidx_create_subset_index(shockidx_ctx *ctx, const void *d_ids, uint64_t ids_len, const void *d_parent,
                                  uint64_t parent_count, int64_t ilength, void *d_rows, uint64_t rows_cap,
                                  shockidx_subset_result *result);
+
+/* ---- subset indexes in slabs and from files ---------------------------------------------------
+ * The same two builders (index/subset.go:133-303 and :36-128) walking the id text slab by slab and
+ * the parent index window by window, so that the device holds two id slots, a parent window, one
+ * slab's workspace and one slab's rows and runs however long the id list is.  subset.go's loop
+ * carries prev_int, prevOffset, prevLength, coOffset, coLength and the three counters from line to
+ * line (:161-176); a slab call takes them from the carry and leaves them in it.
+ *
+ * The id slab (shockidx_slab): d_data 16-byte aligned; n owned bytes, end readable bytes from d_data
+ * (n + halo), front readable bytes before it (at least 16 unless base < 16, then base); base, the
+ * offset of d_data[0] in the id text, may be any offset and n any length; is_first: base == 0;
+ * is_last: base + n == ids_size; seq is ignored.  A line starts at offset 0 or after a '\n'.  The
+ * call owns the lines that start in [max(base, carry.next_off), base + n), carry.next_off being the
+ * first line not yet consumed.  d_carry: shockidx_subset_carry_bytes() bytes of device memory,
+ * 8-byte aligned, zeroed before a walk's first slab, which initialises it (a header and two halves
+ * of the state: a call reads one half and writes the other); the host never reads it.  No byte
+ * outside [d_data - front, d_data + end) is read.
+ *
+ * The parent window: d_parent (16-byte aligned) holds rows [prow0, prow0 + prows) of the parent
+ * index, parent_count is the number of whole rows in the parent file; no row outside the window is
+ * read, the previous id's row comes from the carry.
+ *
+ * A call consumes its owned lines in order exactly as subset.go:186-272 does: a line of at most one
+ * byte is skipped (:197-199), strconv.Atoi of buf[:n-1] (:201-206), the sort check against the
+ * previous accepted id (the carry's for the call's first line, :208-211), the check against ilength
+ * (:213-216), the failed ReadAt, an id above parent_count (:218-223).  Each accepted id's row goes
+ * to d_rows; with want_runs every run closed by a consumed id goes to d_runs as (coOffset, coLength)
+ * (:245-261), the open run stays in the carry, and the last slab, once every line is consumed,
+ * writes the final run iff oSize != 0 (:285-291; rows all of length 0 leave none).  The bytes after
+ * the last '\n' are dropped (:187-195).
+ *
+ * result->stop and result->next_off say where the call stopped; every line before next_off is
+ * consumed and the carry has advanced: 0 all owned lines consumed; 1 the line at next_off does not
+ * close inside the window, which does not reach ids_size; 2 the id at next_off (result->next_id)
+ * passed every check but its row next_id - 1 lies outside the window -- the same slab submitted
+ * again with another window goes on from there.  Of an error line and a stop line the earlier one
+ * decides.
+ *
+ * Returns SHOCKIDX_OK: result->rows / runs written by this call, and the running totals count,
+ * nruns, size (oCount, coCount, oSize).  SHOCKIDX_EFORMAT: Go's text, as shockidx_subset_index
+ * gives it for the whole input; the rows and closed runs before the failing id are written, the
+ * totals are Go's at that point (the open run is not counted), and the walk has ended: any later
+ * call is SHOCKIDX_EINVAL, as is one after the last slab has finished.  SHOCKIDX_ESPACE:
+ * result->rows / runs hold what the call needs, the carry is unchanged, and the same call with
+ * larger tables succeeds.  SHOCKIDX_EINVAL: carry.next_off lies before the slab's first byte (the
+ * line there would belong to no slab) or at or past its last (the walk is past this slab, or the
+ * carry is left from an abandoned walk and was not zeroed), the walk is over, or an argument is
+ * misaligned.  The calls' rows concatenated are shockidx_subset_index's
+ * d_rows, their runs its d_runs, the final totals its totals. */
+typedef struct shockidx_subset_slab_result {
+  uint64_t rows;      /* rows written to d_rows by this call (SHOCKIDX_ESPACE: needed) */
+  uint64_t runs;      /* runs written to d_runs by this call (SHOCKIDX_ESPACE: needed) */
+  uint64_t count;     /* oCount so far */
+  uint64_t nruns;     /* coCount so far */
+  uint64_t size;      /* oSize so far */
+  uint64_t next_off;  /* the line the call stopped at */
+  int64_t next_id;    /* stop 2: the id whose row the window lacks */
+  int32_t stop;       /* 0, 1 or 2 */
+  int32_t status;
+  uint64_t err_len;
+  char err[256];
+  double kernel_ms;
+  double total_ms;
+} shockidx_subset_slab_result;
+uint64_t shockidx_subset_carry_bytes(void);
+int shockidx_subset_slab_device(shockidx_ctx *ctx, const shockidx_slab *ids_slab, uint64_t ids_size,
+                                const void *d_parent, uint64_t prow0, uint64_t prows, uint64_t parent_count,
+                                int64_t ilength, int want_runs, void *d_carry, void *d_rows, uint64_t rows_cap,
+                                void *d_runs, uint64_t runs_cap, shockidx_subset_slab_result *result);
+
+/* The walk over two open descriptors (not closed; pread): id slabs in file order, slab k + 1
+ * crossing PCIe into the second slot while slab k runs (halo 64 KiB); the first parent window
+ * starts at row 0 and after stop 2 the next one starts at row next_id - 1, so sparse lists skip
+ * rows and dense ones abut; parent_count = parent_bytes / 16.  Each call's rows and runs go to the
+ * host as they are made: *rows / *runs receive malloc'ed tables of result->count / result->runs
+ * rows (free with shockidx_free; runs may be NULL without want_runs).  ids_slab_bytes /
+ * parent_slab_rows 0: sized so that the two id slots, the parent window, one slab's workspace (8
+ * bytes per text byte included) and its rows and runs fit the context's device budget
+ * (shockidx_ctx_set_dev_cap); a budget under 32 MiB is SHOCKIDX_ENOMEM, as is an id line longer
+ * than a slab slot can hold.  On SHOCKIDX_EFORMAT the tables hold what was written before the
+ * error and result is as shockidx_subset_index's. */
+int shockidx_subset_fd_walk(shockidx_ctx *ctx, int ids_fd, uint64_t ids_size, int parent_fd, uint64_t parent_bytes,
+                            int64_t ilength, int want_runs, uint64_t ids_slab_bytes, uint64_t parent_slab_rows,
+                            uint64_t **rows, uint64_t **runs, shockidx_subset_result *result);
+/* CreateSubsetNodeIndexes' file protocol (subset.go:136-158,274-297; callers node/fs.go:52-126),
+ * and with cofile == NULL CreateSubsetIndex's (:36-128; node/index.go:103: no runs, and on a Go
+ * error count = size = UINT64_MAX).  Within the budget today's whole build over the uploaded
+ * files, else the walk, which writes each table at 16 * row as it goes.  The tables go through temp
+ * files in tmpdir; cofile is renamed first, then ofile (:293-297).  On any error nothing is left at
+ * either path or in tmpdir (the reference leaves its temp files behind). */
+int shockidx_subset_create(shockidx_ctx *ctx, int ids_fd, uint64_t ids_size, int parent_fd, uint64_t parent_bytes,
+                           int64_t ilength, const char *tmpdir, const char *cofile, const char *ofile,
+                           shockidx_subset_result *result);
+/* how the context's last shockidx_subset_fd_walk / shockidx_subset_create ran */
+typedef struct shockidx_subset_stats {
+  uint64_t walked;       /* 1: the slab walk, 0: the whole build */
+  uint64_t calls;        /* slab calls */
+  uint64_t slabs;        /* id slabs */
+  uint64_t windows;      /* parent windows uploaded */
+  uint64_t ids_bytes;    /* id text bytes sent to the device */
+  uint64_t parent_bytes; /* parent index bytes sent to the device */
+  uint64_t slab_bytes;   /* the id slab size used */
+  uint64_t window_rows;  /* the parent window size used */
+  uint64_t held_bytes;   /* device bytes the context's caches held when the build ended */
+} shockidx_subset_stats;
+int shockidx_subset_last_stats(const shockidx_ctx *ctx, shockidx_subset_stats *out);
 
 /* ---- Index read path: Idx.Part / Idx.Range ----------------------
  * index/index.go:67-117 and :119-193 (callers: controller/node/single.go:391-508,

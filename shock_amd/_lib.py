@@ -38,6 +38,8 @@ EXPORTS = ("shockidx_ctx_create", "shockidx_ctx_destroy", "shockidx_build_device
            "shockidx_chunkrecord_carry_bytes", "shockidx_chunkrecord_slab_device", "shockidx_chunkrecord_fd_walk",
            "shockidx_column_device", "shockidx_column_fd", "shockidx_column_carry_bytes", "shockidx_column_slab_device",
            "shockidx_column_fd_walk", "shockidx_column_create",
+           "shockidx_subset_carry_bytes", "shockidx_subset_slab_device", "shockidx_subset_fd_walk", "shockidx_subset_create",
+           "shockidx_subset_last_stats",
            "shockidx_idx_part", "shockidx_idx_range", "shockidx_filter_device", "shockidx_stream_filter_device", "shockidx_stream_last_stats",
            "shockidx_build_batch_device", "shockidx_build_batch_host", "shockidx_batch_error", "shockidx_batch_last_stats",
            "shockidx_download_plan", "shockidx_ctx_trim",
@@ -96,6 +98,25 @@ class SubsetResult(ctypes.Structure):
     @property
     def message(self) -> bytes:
         return ctypes.string_at(ctypes.addressof(self) + SubsetResult.err.offset, self.err_len)
+
+
+class SubsetSlabResult(ctypes.Structure):
+    """mirrors shockidx_subset_slab_result (include/shockidx.h)"""
+    _fields_ = [("rows", ctypes.c_uint64), ("runs", ctypes.c_uint64), ("count", ctypes.c_uint64),
+                ("nruns", ctypes.c_uint64), ("size", ctypes.c_uint64), ("next_off", ctypes.c_uint64),
+                ("next_id", ctypes.c_int64), ("stop", ctypes.c_int32), ("status", ctypes.c_int32),
+                ("err_len", ctypes.c_uint64), ("err", ctypes.c_char * 256), ("kernel_ms", ctypes.c_double),
+                ("total_ms", ctypes.c_double)]
+
+    @property
+    def message(self) -> bytes:
+        return ctypes.string_at(ctypes.addressof(self) + SubsetSlabResult.err.offset, self.err_len)
+
+
+class SubsetStats(ctypes.Structure):
+    """mirrors shockidx_subset_stats (include/shockidx.h)"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("walked", "calls", "slabs", "windows", "ids_bytes", "parent_bytes",
+                                               "slab_bytes", "window_rows", "held_bytes")]
 
 
 class StreamStats(ctypes.Structure):
@@ -246,6 +267,19 @@ def lib():
     L.shockidx_stream_filter_device.argtypes = [vp, ctypes.c_char_p, vp, u64, vp, u64, vp, u64,
                                                 ctypes.POINTER(ctypes.c_int64), PSub]
     L.shockidx_stream_filter_device.restype = i32
+    PSub_ = ctypes.POINTER(SubsetResult)
+    L.shockidx_subset_carry_bytes.argtypes = []
+    L.shockidx_subset_carry_bytes.restype = u64
+    L.shockidx_subset_slab_device.argtypes = [vp, ctypes.POINTER(Slab), u64, vp, u64, u64, u64, ctypes.c_int64, i32, vp,
+                                              vp, u64, vp, u64, ctypes.POINTER(SubsetSlabResult)]
+    L.shockidx_subset_slab_device.restype = i32
+    L.shockidx_subset_fd_walk.argtypes = [vp, i32, u64, i32, u64, ctypes.c_int64, i32, u64, u64, PPu64, PPu64, PSub_]
+    L.shockidx_subset_fd_walk.restype = i32
+    L.shockidx_subset_create.argtypes = [vp, i32, u64, i32, u64, ctypes.c_int64, ctypes.c_char_p, ctypes.c_char_p,
+                                         ctypes.c_char_p, PSub_]
+    L.shockidx_subset_create.restype = i32
+    L.shockidx_subset_last_stats.argtypes = [vp, ctypes.POINTER(SubsetStats)]
+    L.shockidx_subset_last_stats.restype = i32
     L.shockidx_stream_last_stats.argtypes = [vp, ctypes.POINTER(StreamStats)]
     L.shockidx_stream_last_stats.restype = i32
     PItem = ctypes.POINTER(BatchItem)

@@ -513,6 +513,66 @@ class Context:
                                                     rows_cap, ctypes.byref(r))
         return _sub_result(r, rc)
 
+    # -- subset indexes in slabs and from files (shockidx_subset_slab_device and the walk over it) --
+    def subset_carry(self) -> "DeviceBuffer":
+        """Zeroed device memory for the carry of one subset walk (shockidx_subset_carry_bytes; the first
+        slab initialises it)."""
+        b = self.alloc(int(self._lib.shockidx_subset_carry_bytes()))
+        b.upload(bytes(b.nbytes))
+        return b
+
+    def subset_slab(self, slab: "L.Slab", ids_size: int, d_parent: int, prow0: int, prows: int, parent_count: int,
+                    ilength: int, want_runs: bool, d_carry: int, d_rows: int, rows_cap: int, d_runs: int,
+                    runs_cap: int) -> "L.SubsetSlabResult":
+        """One slab of the id text against one window of the parent index (slabs in file order, the loop's
+        state in the device carry).  Returns the raw result: status OK (rows / runs written, the running
+        totals, stop and next_off / next_id), EFORMAT (Go's text; the walk has ended), ESPACE (rows / runs
+        = what the call needs; the carry is unchanged) or EINVAL."""
+        res = L.SubsetSlabResult()
+        rc = self._lib.shockidx_subset_slab_device(self._h, ctypes.byref(slab), ids_size, d_parent, prow0, prows,
+                                                   parent_count, int(ilength), 1 if want_runs else 0, d_carry, d_rows,
+                                                   rows_cap, d_runs, runs_cap, ctypes.byref(res))
+        if rc < 0 and rc not in (L.EINVAL, L.ESPACE):
+            raise L.ShockIdxError(rc, res.message.decode("utf-8", "replace"))
+        res.status = rc
+        return res
+
+    def subset_fd_walk(self, ids_fd: int, ids_size: int, parent_fd: int, parent_bytes: int, ilength: int,
+                       want_runs: bool = True, ids_slab_bytes: int = 0, parent_slab_rows: int = 0) -> SubsetResult:
+        """The subset builders over two open files, always slab by slab (shockidx_subset_fd_walk; 0: sized
+        to the device budget); rows and run_rows on the host (on EFORMAT: what was written before it)."""
+        r = L.SubsetResult()
+        rows_p, runs_p = ctypes.POINTER(ctypes.c_uint64)(), ctypes.POINTER(ctypes.c_uint64)()
+        rc = self._lib.shockidx_subset_fd_walk(self._h, ids_fd, ids_size, parent_fd, parent_bytes, int(ilength),
+                                               1 if want_runs else 0, ids_slab_bytes, parent_slab_rows,
+                                               ctypes.byref(rows_p), ctypes.byref(runs_p) if want_runs else None,
+                                               ctypes.byref(r))
+        out = _sub_result(r, rc)
+        if rows_p:
+            out.rows = _take_rows(rows_p, out.count)
+        if runs_p:
+            out.run_rows = _take_rows(runs_p, out.runs)
+        return out
+
+    def subset_create(self, ids_fd: int, ids_size: int, parent_fd: int, parent_bytes: int, ilength: int, tmpdir: str,
+                      cofile, ofile: str) -> SubsetResult:
+        """CreateSubsetNodeIndexes with its file protocol (shockidx_subset_create), CreateSubsetIndex's with
+        cofile None: the tables through temp files under tmpdir, cofile renamed first, then ofile; on an
+        error nothing is left behind."""
+        r = L.SubsetResult()
+        rc = self._lib.shockidx_subset_create(self._h, ids_fd, ids_size, parent_fd, parent_bytes, int(ilength),
+                                              os.fsencode(tmpdir), os.fsencode(cofile) if cofile is not None else None,
+                                              os.fsencode(ofile), ctypes.byref(r))
+        return _sub_result(r, rc)
+
+    def subset_stats(self) -> dict:
+        """How the last subset_fd_walk / subset_create ran (shockidx_subset_last_stats)."""
+        st = L.SubsetStats()
+        rc = self._lib.shockidx_subset_last_stats(self._h, ctypes.byref(st))
+        if rc != L.OK:
+            raise L.ShockIdxError(rc, "shockidx_subset_last_stats")
+        return {k: int(getattr(st, k)) for k, _ in L.SubsetStats._fields_}
+
     # -- index read path (index/index.go:67-193) ---------------------------------------------------
     def idx_part(self, d_rows, nrows: int, part: str, idx_length: int):
         """Idx.Part over a device-resident index (d_rows None: the file is missing).

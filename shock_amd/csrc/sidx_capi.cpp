@@ -416,6 +416,169 @@ int shockidx_column_create(shockidx_ctx *c, int fd, uint64_t n, int column, cons
   return SHOCKIDX_OK;
 }
 
+// ---- the subset indexes from files (index/subset.go:36-303) -------------------------------------
+namespace {
+
+// Today's whole build over the two uploaded files: the id text in c->d_in, the parent index in
+// c->d_spar, the rows in c->d_cola and the runs in c->d_sruns (shockidx_subset_index keeps its line
+// ends in c->d_rows); the tables to the sinks.  A table too short for the ids is grown to the
+// count the build reports and the build run again.
+int subset_whole(shockidx_ctx *c, int ids_fd, u64 n, int parent_fd, u64 parent_bytes, i64 ilength, bool want_runs,
+                 SubsetSinks sinks, shockidx_subset_result *res) {
+  hipStream_t s = c->stream;
+  const u64 parent_count = parent_bytes / 16;
+  shockidx_result r1;
+  reset_result(&r1);
+  if (int rc = stage_fd(c, ids_fd, 0, n, s, &r1)) return forward_error(res, r1, rc);
+  if (int rc = c->d_spar.ensure(16 * parent_count + 16, res)) return rc;
+  for (int i = 0; i < 2; ++i)
+    if (!c->h_rows[i]) HIPCHK(hipHostMalloc(&c->h_rows[i], STAGE_BYTES, 0), "hipHostMalloc(rows)");
+  for (u64 done = 0, total = 16 * parent_count; done < total;) {
+    const u64 k = total - done < STAGE_BYTES ? total - done : STAGE_BYTES;
+    for (u64 got = 0; got < k;) {
+      const ssize_t r = pread(parent_fd, c->h_rows[1] + got, k - got, (off_t)(done + got));
+      if (r < 0 && errno == EINTR) continue;
+      if (r <= 0) return set_msg(res, SHOCKIDX_EIO, r < 0 ? strerror(errno) : "unexpected end of file");
+      got += (u64)r;
+    }
+    HIPCHK(hipMemcpyAsync(c->d_spar + done, c->h_rows[1], k, hipMemcpyHostToDevice, s), "parent copy");
+    HIPCHK(hipStreamSynchronize(s), "parent copy");
+    done += k;
+  }
+  u64 rows_cap = n / 8 + 4096, runs_cap = want_runs ? rows_cap : 0;
+  int rc = 0;
+  for (int attempt = 0;; ++attempt) {
+    if (int e = c->d_cola.ensure(16 * rows_cap, res)) return e;
+    if (want_runs)
+      if (int e = c->d_sruns.ensure(16 * runs_cap, res)) return e;
+    rc = shockidx_subset_index(c, c->d_in, n, c->d_spar, parent_count, ilength, c->d_cola, rows_cap,
+                               want_runs ? (void *)c->d_sruns : nullptr, runs_cap, res);
+    if (rc != SHOCKIDX_ESPACE || attempt == 2) break;
+    if (res->count > rows_cap) rows_cap = res->count;
+    if (want_runs && res->runs + 1 > runs_cap) runs_cap = res->runs + 1;
+  }
+  if (rc != SHOCKIDX_OK && rc != SHOCKIDX_EFORMAT) return rc;
+  const shockidx_subset_result keep = *res;
+  const u64 per = STAGE_BYTES / 16;
+  for (int t = 0; t < (want_runs ? 2 : 1); ++t) {
+    const u64 m = t ? keep.runs : keep.count;
+    const u64 *d = t ? (const u64 *)c->d_sruns.as<u64>() : (const u64 *)c->d_cola.as<u64>();
+    for (u64 done = 0; done < m;) {
+      const u64 k = m - done < per ? m - done : per;
+      HIPCHK(hipMemcpyAsync(c->h_rows[0], d + 2 * done, k * 16, hipMemcpyDeviceToHost, s), "rows copy");
+      HIPCHK(hipStreamSynchronize(s), "rows copy");
+      if (int e = (t ? sinks.runs : sinks.rows)->put(c->h_rows[0], done, k, res)) return e;
+      done += k;
+    }
+  }
+  *res = keep;
+  return rc;
+}
+
+}  // namespace
+
+int shockidx_subset_fd_walk(shockidx_ctx *c, int ids_fd, uint64_t ids_size, int parent_fd, uint64_t parent_bytes,
+                            int64_t ilength, int want_runs, uint64_t ids_slab_bytes, uint64_t parent_slab_rows,
+                            uint64_t **rows, uint64_t **runs, shockidx_subset_result *res) {
+  shockidx_subset_result tmp;
+  if (!res) res = &tmp;
+  reset_result(res);
+  if (!c || ids_fd < 0 || parent_fd < 0 || !rows || (want_runs && !runs))
+    return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+  *rows = nullptr;
+  if (runs) *runs = nullptr;
+  TrimGuard trim{c};
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  TableSink srows(ids_size), sruns(want_runs ? ids_size : 0);
+  if (!srows.out || !sruns.out) return set_msg(res, SHOCKIDX_ENOMEM, "out of host memory");
+  const int rc = subset_fd_walk(c, ids_fd, ids_size, parent_fd, parent_bytes, ilength, want_runs != 0, ids_slab_bytes,
+                                parent_slab_rows, SubsetSinks{&srows, &sruns}, res);
+  if (rc != SHOCKIDX_OK && rc != SHOCKIDX_EFORMAT) return rc;
+  *rows = (uint64_t *)srows.out;
+  srows.out = nullptr;
+  if (want_runs) {
+    *runs = (uint64_t *)sruns.out;
+    sruns.out = nullptr;
+  }
+  return rc;
+}
+
+// CreateSubsetNodeIndexes' file protocol (subset.go:136-158,274-297), CreateSubsetIndex's with
+// cofile == NULL (:36-128).  Within the device budget the whole build over the uploaded files,
+// else the walk, which writes both tables at 16 * row as its calls deliver them.  Whatever ends the
+// build early takes both temp files with it (the reference leaves them in conf.PATH_DATA/temp).
+int shockidx_subset_create(shockidx_ctx *c, int ids_fd, uint64_t ids_size, int parent_fd, uint64_t parent_bytes,
+                           int64_t ilength, const char *tmpdir, const char *cofile, const char *ofile,
+                           shockidx_subset_result *res) {
+  shockidx_subset_result tmp;
+  if (!res) res = &tmp;
+  reset_result(res);
+  if (!c || ids_fd < 0 || parent_fd < 0 || !tmpdir || !ofile) return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  TrimGuard trim{c};
+  const bool want_runs = cofile != nullptr;
+  FileSink srows, sruns;
+  const std::string opath = temp_idx_path(tmpdir), copath = want_runs ? temp_idx_path(tmpdir) : std::string();
+  srows.fd = open(opath.c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0666);
+  if (srows.fd < 0) return set_msg(res, SHOCKIDX_EIO, std::string("create: ") + strerror(errno));
+  if (want_runs) {
+    sruns.fd = open(copath.c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0666);
+    if (sruns.fd < 0) {
+      const int e = errno;
+      close(srows.fd);
+      unlink(opath.c_str());
+      return set_msg(res, SHOCKIDX_EIO, std::string("create: ") + strerror(e));
+    }
+  }
+  int rc;
+  if (subset_whole_bytes(ids_size, parent_bytes) <= dev_budget(c)) {
+    memset(&c->subset_stats, 0, sizeof c->subset_stats);
+    rc = subset_whole(c, ids_fd, ids_size, parent_fd, parent_bytes, ilength, want_runs, SubsetSinks{&srows, &sruns}, res);
+    c->subset_stats.ids_bytes = ids_size;
+    c->subset_stats.parent_bytes = parent_bytes / 16 * 16;
+    c->subset_stats.held_bytes = workspace_bytes(c);
+  } else {
+    rc = subset_fd_walk(c, ids_fd, ids_size, parent_fd, parent_bytes, ilength, want_runs, 0, 0,
+                        SubsetSinks{&srows, &sruns}, res);
+  }
+  int ce = close(srows.fd);
+  if (want_runs && close(sruns.fd) != 0) ce = -1;
+  const int e0 = errno;
+  auto drop = [&]() {
+    unlink(opath.c_str());
+    if (want_runs) unlink(copath.c_str());
+  };
+  if (rc != SHOCKIDX_OK) {
+    drop();
+    if (rc == SHOCKIDX_EFORMAT && !want_runs) res->count = res->size = ~0ull;  // (-1, -1, err): subset.go:36-128
+    if (!want_runs) res->runs = 0;
+    return rc;
+  }
+  if (ce != 0) {
+    drop();
+    return set_msg(res, SHOCKIDX_EIO, std::string("close: ") + strerror(e0));
+  }
+  if (want_runs && rename(copath.c_str(), cofile) != 0) {  // :293
+    const int e = errno;
+    drop();
+    return set_msg(res, SHOCKIDX_EIO, std::string("rename: ") + strerror(e));
+  }
+  if (rename(opath.c_str(), ofile) != 0) {  // :297
+    const int e = errno;
+    drop();
+    if (want_runs) unlink(cofile);
+    return set_msg(res, SHOCKIDX_EIO, std::string("rename: ") + strerror(e));
+  }
+  if (!want_runs) res->runs = 0;
+  return SHOCKIDX_OK;
+}
+
+int shockidx_subset_last_stats(const shockidx_ctx *c, shockidx_subset_stats *out) {
+  if (!c || !out) return SHOCKIDX_EINVAL;
+  *out = c->subset_stats;
+  return SHOCKIDX_OK;
+}
+
 int shockidx_dev_alloc(shockidx_ctx *c, uint64_t bytes, void **d_ptr) {
   if (!c || !d_ptr) return SHOCKIDX_EINVAL;
   if (hipSetDevice(c->device) != hipSuccess) return SHOCKIDX_EHIP;

@@ -133,6 +133,10 @@ struct shockidx_ctx {
   Buf<uint8_t> d_batch{bufs};      // batch build: per-node formats, counts, first rows, slots, items, singles (bytes)
   Buf<uint8_t> d_bnodes{bufs};     //   the host entry point's node list (bytes)
   shockidx_batch_stats batch_stats = {};  //   how the last batch call ran (shockidx_batch_last_stats)
+  Buf<uint8_t> d_sends{bufs};      // subset slab call: the window's line ends, their counts and scan workspace (bytes)
+  Buf<uint8_t> d_spar{bufs};       // subset walk: the parent window (bytes)
+  Buf<uint8_t> d_sruns{bufs};      //   the carry, then one slab's runs (bytes)
+  shockidx_subset_stats subset_stats = {};  //   how the last file-level subset build ran (shockidx_subset_last_stats)
   hipStream_t s_copy = nullptr;    // slab-pipelined host builds: the H2D stream
   uint8_t *h_rows[2] = {nullptr, nullptr};  // slab-pipelined fd builds: pinned row staging (D2H)
   // download filters over FASTQ: the tile pass keeps each record's line ends (k_fq_tiles<true>)
@@ -332,6 +336,24 @@ sidx::ChunkWalkDev chunk_walk_dev(shockidx_ctx *c, sidx::u64 len);
 // the sink slab by slab.  result->path 6.
 int chunk_fd_walk(shockidx_ctx *c, int fd, sidx::u64 n, int fmt, sidx::u64 chunk, sidx::u64 S, RowSink &sink,
                   shockidx_result *res);
+
+// ---- the subset indexes in slabs (sidx_subset_api.cpp, sidx_pipeline.cpp) ----------------------
+// device bytes one slab call over a window of `end` readable bytes takes from the context's caches
+// (c->d_sends, c->d_sub): 8 bytes per text byte for the line ends, the per-line arrays, the scans
+sidx::u64 subset_slab_ws_bytes(sidx::u64 end);
+void subset_slab_ws_parts(sidx::u64 end, sidx::u64 *ends_bytes, sidx::u64 *line_bytes);  // (c->d_sends, c->d_sub)
+// what the whole build (shockidx_subset_index over the uploaded files) holds at its peak
+sidx::u64 subset_whole_bytes(sidx::u64 ids_size, sidx::u64 parent_bytes);
+// Where a walk's rows and runs go as each call delivers them (tables or temp files): first = the
+// number of the first row / run of the piece
+struct SubsetSinks {
+  RowSink *rows, *runs;
+};
+// The walk over the two files: S-byte id slabs, W-row parent windows (0: sized from the device
+// budget).  result as shockidx_subset_index's; c->subset_stats says how it ran.
+int subset_fd_walk(shockidx_ctx *c, int ids_fd, sidx::u64 ids_size, int parent_fd, sidx::u64 parent_bytes,
+                   sidx::i64 ilength, bool want_runs, sidx::u64 S, sidx::u64 W, SubsetSinks sinks,
+                   shockidx_subset_result *res);
 
 // *done = false: not applicable, the caller runs the plain path
 int build_host_pipelined(shockidx_ctx *c, const void *data, sidx::u64 n, int kind, int fmt, uint64_t **rows,

@@ -10,6 +10,7 @@
 
 #include "sidx_batch.hpp"
 #include "sidx_common.hpp"
+#include "sidx_subset.hpp"
 
 extern "C" {
 
@@ -117,6 +118,10 @@ hipError_t sidx_subset_check(const sidx::i64 *cval, const sidx::u32 *cst, sidx::
     sidx::u32 *startf, hipStream_t s);
 hipError_t sidx_subset_runs(const sidx::u64 *rows, const sidx::u32 *startf, const sidx::u64 *runid, sidx::u64 m,
     sidx::u64 *ctl, sidx::u64 *runs, sidx::u64 rows_cap, sidx::u64 runs_cap, hipStream_t s);
+// the subset walk's slab call (sidx_subset.hip): up to its host stop (the SL_* control words), then
+// the closed runs and the carry
+hipError_t sidx_subs_plan(const sidx::SubSlabArgs *a, void *scan_tmp, size_t *scan_bytes, hipStream_t s);
+hipError_t sidx_subs_commit(const sidx::SubSlabArgs *a, sidx::u64 ke, sidx::u64 nclosed, hipStream_t s);
 hipError_t sidx_launch_fq_spans_place(const sidx::SlabParams *pp, sidx::u32 *spans, sidx::u64 *outlen, sidx::u64 K,
     int kind, hipStream_t s);
 hipError_t sidx_filter_spans(const uint8_t *data, sidx::u64 n, const sidx::u64 *rows, sidx::u64 K, int kind,

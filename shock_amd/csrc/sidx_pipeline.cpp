@@ -53,6 +53,7 @@
 #include "sidx_slabwalk.hpp"
 #include "sidx_colwalk.hpp"
 #include "sidx_chunkwalk.hpp"
+#include "sidx_subwalk.hpp"
 #include "sidx_launch.hpp"
 #include "sidx_host.hpp"
 
@@ -783,6 +784,171 @@ int column_fd_walk(shockidx_ctx *c, int fd, u64 n, u32 column, u64 S, u64 halo, 
   res->h2d_ms = res->total_ms - t_d2h - res->kernel_ms;
   res->status = SHOCKIDX_OK;
   return SHOCKIDX_OK;
+}
+
+// ---- the subset indexes' walk ------------------------------------------------------------------
+// CreateSubsetNodeIndexes / CreateSubsetIndex (subset.go:186-291) over the two files: the id text
+// slab by slab through the two slots (slab k + 1 copied on the copy stream while slab k runs), the
+// parent index window by window (pread, as the reference's ReadAt per id: the first window from row
+// 0, after a stop at an id the next from that id's row), each call's rows and runs to the sinks as
+// they are made, the loop's state in the device carry.  sidx_subwalk.hpp holds the sizing and the
+// decisions.  The device holds the two slots, the window, the carry with one slab's runs, one
+// call's workspace (c->d_sends, c->d_sub) and one slab's rows, all sized up front.
+namespace {
+
+// m rows of a device table through a pinned buffer into a sink, numbered from `first`
+int sub_table_to_sink(shockidx_ctx *c, const u64 *d_tab, u64 m, u64 first, RowSink &sink, Err res) {
+  const u64 per = STAGE_BYTES / 16;
+  for (u64 done = 0; done < m;) {
+    const u64 k = m - done < per ? m - done : per;
+    HIPCHK(hipMemcpyAsync(c->h_rows[0], d_tab + 2 * done, k * 16, hipMemcpyDeviceToHost, c->stream), "rows copy");
+    HIPCHK(hipStreamSynchronize(c->stream), "rows copy");
+    if (int rc = sink.put(c->h_rows[0], first + done, k, res)) return rc;
+    done += k;
+  }
+  return 0;
+}
+
+// rows [w.row0, w.row0 + w.rows) of the parent index file into the window buffer
+int sub_load_window(shockidx_ctx *c, int fd, const SubWindow &w, Err res) {
+  const u64 per = STAGE_BYTES;
+  for (u64 done = 0, total = 16 * w.rows; done < total;) {
+    const u64 k = total - done < per ? total - done : per;
+    for (u64 got = 0; got < k;) {
+      const ssize_t r = pread(fd, c->h_rows[1] + got, k - got, (off_t)(16 * w.row0 + done + got));
+      if (r < 0 && errno == EINTR) continue;
+      if (r < 0) return set_msg(res, SHOCKIDX_EIO, std::string("read: ") + strerror(errno));
+      if (r == 0) return set_msg(res, SHOCKIDX_EIO, "read: the parent index file is shorter than its size");
+      got += (u64)r;
+    }
+    HIPCHK(hipMemcpyAsync(c->d_spar + done, c->h_rows[1], k, hipMemcpyHostToDevice, c->stream), "window copy");
+    HIPCHK(hipStreamSynchronize(c->stream), "window copy");
+    done += k;
+  }
+  return 0;
+}
+
+}  // namespace
+
+int subset_fd_walk(shockidx_ctx *c, int ids_fd, u64 n, int parent_fd, u64 parent_bytes, i64 ilength, bool want_runs,
+                   u64 S, u64 W, SubsetSinks sinks, shockidx_subset_result *res) {
+  const double t0 = now_ms();
+  shockidx_subset_stats &st = c->subset_stats;
+  memset(&st, 0, sizeof st);
+  st.walked = 1;
+  if (!n) return SHOCKIDX_OK;  // no line: two empty tables (:186-195,274-291)
+  const u64 parent_count = parent_bytes / 16, budget = dev_budget(c);
+  const u64 carry_b = (sizeof(SubCarry) + 255) & ~255ull;
+  u64 halo = SUBWALK_HALO < n ? SUBWALK_HALO : n;
+  if (!W) W = subwalk_window_rows(budget, parent_count);
+  if (W > parent_count) W = parent_count ? parent_count : 1;
+  if (!S) {
+    S = subwalk_slab_bytes(budget, halo, W, carry_b, subset_slab_ws_bytes);
+    if (!S) return set_msg(res, SHOCKIDX_ENOMEM, "device memory: the subset walk needs at least 32 MiB of its budget");
+  }
+  if (S > n) S = n;
+  st.slab_bytes = S;
+  st.window_rows = W;
+  hipStream_t s = c->stream;
+  if (!c->s_copy) HIPCHK(hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking), "copy stream");
+  for (int i = 0; i < 2; ++i)
+    if (!c->h_rows[i]) HIPCHK(hipHostMalloc(&c->h_rows[i], STAGE_BYTES, 0), "hipHostMalloc(rows)");
+  const u64 slot = subwalk_slot_bytes(S, halo), rows_cap = subwalk_rows_cap(S), runs_cap = subwalk_runs_cap(S);
+  u64 ends_b = 0, line_b = 0;  // a call's workspace, sized for the longest window so that no call grows it
+  subset_slab_ws_parts(S + halo, &ends_b, &line_b);
+  if (c->d_slot[0].cap != slot || c->d_slot[1].cap != slot || c->d_spar.cap != 16 * W || c->d_rows.cap != rows_cap ||
+      c->d_sruns.cap != carry_b + 16 * runs_cap || c->d_sends.cap != ends_b || c->d_sub.cap != line_b) {
+    trim_workspace(c, 0);  // the caches of other builds go first
+    for (auto &sl : c->d_slot)
+      if (int rc = sl.exact(slot, res)) return rc;
+    if (int rc = c->d_spar.exact(16 * W, res)) return rc;
+    if (int rc = c->d_rows.exact(rows_cap, res)) return rc;
+    if (int rc = c->d_sruns.exact(carry_b + 16 * runs_cap, res)) return rc;
+    if (int rc = c->d_sends.exact(ends_b, res)) return rc;
+    if (int rc = c->d_sub.exact(line_b, res)) return rc;
+  }
+  SubCarry *carry = c->d_sruns.as<SubCarry>();
+  u64 *d_runs = (u64 *)(c->d_sruns + carry_b);
+  HIPCHK(hipMemsetAsync(carry, 0, carry_b, s), "carry");
+  SlabEvents events(2, c->s_copy);  // (outlives the source's copies)
+  HIPCHK(events.create(), "event");
+  PageCacheSource src(c, ids_fd, 0, n, res);
+  ColWalk w{c, n, S, halo, events, src, res};
+  SubCursor cur;
+  SubWindow win = subwalk_window_at(0, W, parent_count);
+  int rc = sub_load_window(c, parent_fd, win, res);
+  st.windows = 1;
+  st.parent_bytes = 16 * win.rows;
+  int i = 0;
+  ColSlabPos p = colwalk_slab_at(0, S, halo, n);
+  if (!rc) rc = w.stage(0, p);
+  st.ids_bytes = p.end;
+  shockidx_subset_slab_result r2;
+  memset(&r2, 0, sizeof r2);
+  while (!rc) {
+    bool more = !p.last, moved = false;
+    ColSlabPos q = p;
+    if (more) {  // the slab expected next, on its way while this one runs
+      q = colwalk_slab_at(p.lo + p.n, S, halo, n);
+      if ((rc = w.stage(i ^ 1, q))) break;
+      st.ids_bytes += q.end + q.front;
+    }
+    if (hipError_t e = hipStreamWaitEvent(s, events.ev[i], 0)) { rc = set_hip(res, e, "wait slab"); break; }
+    st.slabs++;
+    for (;;) {
+      shockidx_slab sl;
+      memset(&sl, 0, sizeof sl);
+      sl.d_data = c->d_slot[i] + COLWALK_FRONT;
+      sl.n = p.n; sl.end = p.end; sl.front = p.front; sl.base = p.lo;
+      sl.is_first = p.first; sl.is_last = p.last;
+      rc = shockidx_subset_slab_device(c, &sl, n, c->d_spar, win.row0, win.rows, parent_count, ilength, want_runs, carry,
+                                       c->d_rows, rows_cap, d_runs, runs_cap, &r2);
+      st.calls++;
+      res->kernel_ms += r2.kernel_ms;
+      if (rc != SHOCKIDX_OK && rc != SHOCKIDX_EFORMAT) {
+        if (rc == SHOCKIDX_ESPACE) rc = set_msg(res, SHOCKIDX_EINTERNAL, "internal error: a slab's tables are short");
+        else forward_error(res, r2, rc);
+        break;
+      }
+      const int rc_call = rc;
+      if ((rc = sub_table_to_sink(c, c->d_rows, r2.rows, cur.take_rows(r2.rows), *sinks.rows, res))) break;
+      if (want_runs && (rc = sub_table_to_sink(c, d_runs, r2.runs, cur.take_runs(r2.runs), *sinks.runs, res))) break;
+      if (rc_call == SHOCKIDX_EFORMAT) { rc = forward_error(res, r2, SHOCKIDX_EFORMAT); break; }
+      if (r2.stop == 2) {  // the same slab against the window that starts at the id's row
+        win = subwalk_next_window(r2.next_id, W, parent_count);
+        if ((rc = sub_load_window(c, parent_fd, win, res))) break;
+        st.windows++;
+        st.parent_bytes += 16 * win.rows;
+        continue;
+      }
+      if (r2.stop == 1) {
+        if (subwalk_on_open_line(p.lo, r2.next_off) == SubRetry::NoMem) {
+          rc = set_msg(res, SHOCKIDX_ENOMEM, "device memory: an id line is longer than a slab slot can hold");
+          break;
+        }
+        q = colwalk_slab_at(r2.next_off, S, halo, n);
+        more = moved = true;
+      }
+      break;
+    }
+    if (rc || !more) break;
+    if (moved) {  // a fresh slot from the open line on
+      if ((rc = w.stage(i ^ 1, q))) break;
+      st.ids_bytes += q.end + q.front;
+    }
+    p = q;
+    i ^= 1;
+  }
+  const hipError_t se = src.drain();  // before the pages are unpinned and unmapped
+  if (se != hipSuccess && rc >= 0 && rc != SHOCKIDX_EFORMAT) rc = set_hip(res, se, "H2D sync");
+  st.held_bytes = workspace_bytes(c);
+  if (rc == SHOCKIDX_OK || rc == SHOCKIDX_EFORMAT) {
+    res->count = r2.count;
+    res->runs = r2.nruns;
+    res->size = r2.size;
+  }
+  res->total_ms = now_ms() - t0;
+  return rc;
 }
 
 // ---- the chunkrecord index's walk --------------------------------------------------------------

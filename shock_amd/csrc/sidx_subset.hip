@@ -233,6 +233,233 @@ __global__ void k_sub_run_len(const u64 *rows, const u32 *startf, const u64 *run
   }
 }
 
+// ---- the same loop one slab of the id text at a time (shockidx_subset_slab_device) ------------
+// The slab's '\n's are found over [text, text + end) (k_idl_*), so line j of the window is
+// [ends[j - 1] + 1, ends[j]], the first from the slab's first byte -- a line only when the byte
+// before it is a '\n' (or the file starts there).  The slab owns the lines that start in
+// [max(base, carry.next_off), base + n); the others are never parsed.  subset.go:168-176's state
+// enters at rank 0 from the carry (SubCarryHalf) and leaves through k_subs_commit.
+__device__ __forceinline__ u64 subs_line_off(const SubSlabArgs &a, u64 j) { return j ? a.ends[j - 1] + 1 : 0; }
+__device__ __forceinline__ u64 subs_ke(const u64 *ctl) {  // ids consumed: up to the first failing or outside one
+  u64 ke = ctl[SL_K];
+  const u64 fb = ctl[SL_FIRSTBAD], fo = ctl[SL_FIRSTOUT];
+  if (fb != ~0ull && (fb >> 3) < ke) ke = fb >> 3;
+  return fo < ke ? fo : ke;
+}
+
+// one thread: the control words, the carry of a first slab, what the carry allows, the window's open last line
+__global__ void k_subs_begin(SubSlabArgs a) {
+  if (threadIdx.x || blockIdx.x) return;
+  u64 *ctl = a.ctl;
+  for (int i = 0; i < SL_WORDS; ++i) ctl[i] = (i == SL_FIRSTBAD || i == SL_FIRSTOUT || i == SL_TAIL) ? ~0ull : 0;
+  SubCarry *c = a.carry;
+  if (a.is_first && c->magic != SUBCARRY_MAGIC) {  // the walk's first call
+    for (int k = 0; k < 2; ++k) {
+      SubCarryHalf z;
+      z.next_off = 0; z.prev_id = 0; z.prev_off = 0; z.prev_len = 0; z.co_off = 0; z.count = 0; z.nruns = 0; z.size = 0;
+      c->half[k] = z;
+    }
+    c->which = 0;
+    c->state = SW_WALK;
+    c->magic = SUBCARRY_MAGIC;
+  }
+  if (c->magic != SUBCARRY_MAGIC || c->state != SW_WALK) { ctl[SL_FLAGS] = 1; return; }
+  const u64 next_off = c->half[c->which & 1].next_off;
+  // A line that starts before the slab is nobody's any more (ownership begins at base), and a slab
+  // the walk is already past was submitted out of order -- or the carry is an abandoned walk's
+  // that was not zeroed: refuse both instead of dropping a line or continuing stale totals.
+  if (next_off < a.base || (a.n && next_off >= a.base + a.n)) { ctl[SL_FLAGS] = 1; return; }
+  const u64 S = next_off > a.base ? next_off - a.base : 0;
+  const bool ls = a.base == 0 || a.text[-1] == '\n';
+  const u64 tail = a.m ? a.ends[a.m - 1] + 1 : (ls ? 0 : ~0ull);
+  // the bytes after the window's last '\n': an owned line still open, unless the file ends there (:187-195)
+  if (tail != ~0ull && tail < a.n && tail >= S && a.base + a.end != a.ids_size) ctl[SL_TAIL] = tail;
+  ctl[SL_START] = S;
+  ctl[SL_BASE_LS] = ls;
+}
+
+// k_sub_parse over the owned lines; the others count as blank
+__global__ void k_subs_parse(SubSlabArgs a) {
+  const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= a.m) return;
+  const u64 off = subs_line_off(a, j), len = a.ends[j] + 1 - off;
+  const bool owned = !a.ctl[SL_FLAGS] && off >= a.ctl[SL_START] && off < a.n && (j > 0 || a.ctl[SL_BASE_LS]);
+  const bool k = owned && len > 1;
+  i64 v = 0;
+  u32 s = SUB_OK;
+  if (k) s = go_atoi(a.text + off, len - 1, v);
+  a.keep[j] = k;
+  a.val[j] = v;
+  a.st[j] = s;
+}
+
+// k_sub_check with the carry at rank 0 and the parent index as a window: the first id whose row the
+// window does not hold is reduced beside the first failing one (the earlier of the two ends the call)
+__global__ void k_subs_check(SubSlabArgs a) {
+  const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  u64 *ctl = a.ctl;
+  const bool in = r < ctl[SL_K];
+  const SubCarryHalf h = a.carry->half[a.carry->which & 1];
+  i64 v = 0, prev = 0;
+  u32 code = SUB_SORT;
+  if (in) {
+    v = a.cval[r];
+    prev = r ? a.cval[r - 1] : h.prev_id;
+    code = a.cst[r];
+    if (code == SUB_OK) {
+      if (v <= prev) code = SUB_SORT;                          // :208-211
+      else if (v > a.ilength) code = SUB_EXIST;                // :213-216
+      else if ((u64)v > a.parent_count) code = SUB_READ;       // :218-223
+    }
+  }
+  const bool ok = in && code == SUB_OK;
+  const bool inw = ok && (u64)(v - 1) >= a.prow0 && (u64)(v - 1) - a.prow0 < a.prows;
+  ulonglong2 row = make_ulonglong2(0, 0);
+  if (inw) row = reinterpret_cast<const ulonglong2 *>(a.parent)[(u64)(v - 1) - a.prow0];
+  const u32 px0 = (u32)__shfl_up((int)(u32)row.x, 1, 64), px1 = (u32)__shfl_up((int)(u32)(row.x >> 32), 1, 64);
+  const u32 py0 = (u32)__shfl_up((int)(u32)row.y, 1, 64), py1 = (u32)__shfl_up((int)(u32)(row.y >> 32), 1, 64);
+  const bool inwprev = __shfl_up((int)inw, 1, 64) != 0;
+  if (!in) return;
+  u32 *startf = a.keep;
+  startf[r] = 0;
+  if (!ok) {
+    atomicMin(ctl + SL_FIRSTBAD, (r << 3) | code);
+    return;
+  }
+  if (!inw) {
+    atomicMin(ctl + SL_FIRSTOUT, r);
+    return;
+  }
+  if (r < a.rows_cap) reinterpret_cast<ulonglong2 *>(a.rows)[r] = row;
+  if (!a.want_runs) return;
+  // :245 prev_int != 0 && offset != prevOffset + prevLength: this id closes the open run
+  bool have = false;
+  ulonglong2 pr = make_ulonglong2(0, 0);
+  if (r == 0) {
+    have = h.count != 0;
+    pr = make_ulonglong2(h.prev_off, h.prev_len);
+  } else if (lane > 0 && inwprev) {
+    have = true;
+    pr = make_ulonglong2((u64)px0 | ((u64)px1 << 32), (u64)py0 | ((u64)py1 << 32));
+  } else if (prev >= 1 && (u64)(prev - 1) >= a.prow0 && (u64)(prev - 1) - a.prow0 < a.prows) {
+    have = true;
+    pr = reinterpret_cast<const ulonglong2 *>(a.parent)[(u64)(prev - 1) - a.prow0];
+  }
+  startf[r] = have && row.x != pr.x + pr.y;
+}
+
+// oSize of the consumed ids (block sum, one atomic per block).  The lengths come from the parent
+// window, not from d_rows: a table too short for the call (ESPACE) must not change the sum, which
+// decides whether the final run is needed.
+__global__ void k_subs_size(SubSlabArgs a) {
+  const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  const u64 ke = subs_ke(a.ctl);
+  u64 x = r < ke ? a.parent[2 * ((u64)(a.cval[r] - 1) - a.prow0) + 1] : 0;  // (a consumed id's row is in the window)
+  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
+  __shared__ u64 part[4];
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = x;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 t = 0;
+    for (u32 w = 0; w < blockDim.x / 64; ++w) t += part[w];
+    if (t) atomicAdd((unsigned long long *)(a.ctl + SL_SIZE), (unsigned long long)t);
+  }
+}
+
+// one thread: where the call stops and what it would write (the host checks the capacities next)
+__global__ void k_subs_plan(SubSlabArgs a) {
+  if (threadIdx.x || blockIdx.x) return;
+  u64 *ctl = a.ctl;
+  if (ctl[SL_FLAGS]) return;
+  const SubCarryHalf h = a.carry->half[a.carry->which & 1];
+  const u64 ke = subs_ke(ctl), fb = ctl[SL_FIRSTBAD], fo = ctl[SL_FIRSTOUT];
+  const bool err = fb != ~0ull && (fb >> 3) == ke;
+  u64 stop = 0, next_off = h.next_off > a.base + a.n ? h.next_off : a.base + a.n;
+  if (err) {
+    const u64 j = a.cline[ke], off = subs_line_off(a, j);
+    ctl[SL_CODE] = fb & 7;
+    ctl[SL_ERR_V] = (u64)a.cval[ke];
+    ctl[SL_ERR_PREV] = (u64)(ke ? a.cval[ke - 1] : h.prev_id);
+    ctl[SL_ERR_OFF] = off;
+    ctl[SL_ERR_LEN] = a.ends[j] - off;
+    next_off = a.base + off;
+  } else if (fo != ~0ull) {
+    stop = 2;
+    next_off = a.base + subs_line_off(a, a.cline[fo]);
+    ctl[SL_NEXT_ID] = (u64)a.cval[fo];
+  } else if (ctl[SL_TAIL] != ~0ull) {
+    stop = 1;
+    next_off = a.base + ctl[SL_TAIL];
+  }
+  const u64 nclosed = (a.want_runs && ke) ? a.rank[ke - 1] + a.keep[ke - 1] : 0;
+  const u64 tot = h.size + ctl[SL_SIZE];
+  const u64 fin = (!err && stop == 0 && a.is_last && a.want_runs && tot != 0) ? 1 : 0;  // :285-291
+  ctl[SL_KE] = ke;
+  ctl[SL_STOP] = stop;
+  ctl[SL_NEXT_OFF] = next_off;
+  ctl[SL_NCLOSED] = nclosed;
+  ctl[SL_FINAL] = fin;
+  ctl[SL_COUNT] = h.count + ke;
+  ctl[SL_NRUNS] = h.nruns + nclosed + fin;
+  ctl[SL_TOTSIZE] = tot;
+}
+
+// the runs closed by this call's ids (:245-261): run j is closed by the j-th run start, which
+// opens run j + 1 (the last one stays open: SL_NEWCO); run 0 is the one carried in open, or the
+// walk's first
+__global__ void k_subs_run_off(SubSlabArgs a) {
+  const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  const u64 ke = a.ctl[SL_KE], nclosed = a.ctl[SL_NCLOSED];
+  if (r >= ke) return;
+  if (r == 0 && nclosed) {
+    const SubCarryHalf &h = a.carry->half[a.carry->which & 1];
+    a.runs[0] = h.count ? h.co_off : a.rows[0];
+  }
+  if (!a.keep[r]) return;
+  const u64 j = a.rank[r];
+  if (j + 1 < nclosed) a.runs[2 * (j + 1)] = a.rows[2 * r];
+  else a.ctl[SL_NEWCO] = a.rows[2 * r];
+}
+__global__ void k_subs_run_len(SubSlabArgs a) {
+  const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.ctl[SL_KE] || !a.keep[r]) return;
+  const SubCarryHalf &h = a.carry->half[a.carry->which & 1];
+  const u64 end = r ? a.rows[2 * r - 2] + a.rows[2 * r - 1] : h.prev_off + h.prev_len;
+  const u64 j = a.rank[r];
+  a.runs[2 * j + 1] = end - a.runs[2 * j];  // coLength: the run's lengths summed (mod 2^64)
+}
+
+// one thread, ordinary stores: the state after this call into the other half, the final run, the flip
+__global__ void k_subs_commit(SubSlabArgs a) {
+  if (threadIdx.x || blockIdx.x) return;
+  const u64 *ctl = a.ctl;
+  SubCarry *c = a.carry;
+  const u32 w = c->which & 1;
+  const SubCarryHalf h = c->half[w];
+  const u64 ke = ctl[SL_KE], nclosed = ctl[SL_NCLOSED];
+  SubCarryHalf o = h;
+  o.next_off = ctl[SL_NEXT_OFF];
+  if (ke) {
+    o.prev_id = a.cval[ke - 1];
+    o.prev_off = a.rows[2 * ke - 2];
+    o.prev_len = a.rows[2 * ke - 1];
+    if (nclosed) o.co_off = ctl[SL_NEWCO];
+    else if (!h.count) o.co_off = a.rows[0];
+  }
+  o.count = ctl[SL_COUNT];
+  o.nruns = ctl[SL_NRUNS];
+  o.size = ctl[SL_TOTSIZE];
+  if (ctl[SL_FINAL]) {
+    a.runs[2 * nclosed] = o.co_off;
+    a.runs[2 * nclosed + 1] = o.prev_off + o.prev_len - o.co_off;
+  }
+  c->half[w ^ 1] = o;
+  c->which = w ^ 1;
+  if (ctl[SL_CODE]) c->state = SW_ERROR;
+  else if (a.is_last && ctl[SL_STOP] == 0) c->state = SW_DONE;
+}
+
 // ---- Idx.Range (index/index.go:119-193) ---------------------------------------------------
 // Range reads rows a-1 .. b-1 of the .idx file in order into one reused `rec` slice; a read
 // past the end of the file fails and leaves rec as it was, so row i reads as rows[i] for
@@ -623,5 +850,38 @@ extern "C" hipError_t sidx_range_emit(const u64 *rows, u64 nrows, u64 a0, u64 nr
     hipLaunchKernelGGL(k_range_pos, dim3(nblk(nr, 256)), dim3(256), 0, s, rows, nrows, a0, nr, flags, id, recs);
     hipLaunchKernelGGL(k_range_len, dim3(nblk(nr, 256)), dim3(256), 0, s, rows, nrows, a0, nr, flags, id, recs);
   }
+  return hipGetLastError();
+}
+
+// One slab call up to its host stop: the carry's say, the owned lines parsed and compacted, the
+// checks against the parent window, oSize, the run starts' scan and the plan (SL_* words).  a->m
+// is the window's '\n' count (sidx_id_lines ran before).
+extern "C" hipError_t sidx_subs_plan(const SubSlabArgs *a, void *scan_tmp, size_t *scan_bytes, hipStream_t s) {
+  const u64 m = a->m;
+  hipLaunchKernelGGL(k_subs_begin, dim3(1), dim3(64), 0, s, *a);
+  if (m) {
+    const dim3 g(nblk(m, 256)), b(256);
+    hipLaunchKernelGGL(k_subs_parse, g, b, 0, s, *a);
+    hipError_t e = dscan::run<u32, dscan::Sum, true>(scan_tmp, scan_bytes, a->keep, a->rank, m, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_sub_compact, g, b, 0, s, a->keep, a->rank, a->val, a->st, m, a->cval, a->cst, a->cline, a->ctl);
+    hipLaunchKernelGGL(k_subs_check, g, b, 0, s, *a);
+    hipLaunchKernelGGL(k_subs_size, g, b, 0, s, *a);
+    if (a->want_runs) {
+      e = dscan::run<u32, dscan::Sum, true>(scan_tmp, scan_bytes, a->keep, a->rank, m, s);
+      if (e != hipSuccess) return e;
+    }
+  }
+  hipLaunchKernelGGL(k_subs_plan, dim3(1), dim3(64), 0, s, *a);
+  return hipGetLastError();
+}
+// The rest of the call, once the host has seen that the tables hold it: the ke consumed ids' closed
+// runs, then the carry.
+extern "C" hipError_t sidx_subs_commit(const SubSlabArgs *a, u64 ke, u64 nclosed, hipStream_t s) {
+  if (ke && nclosed) {
+    hipLaunchKernelGGL(k_subs_run_off, dim3(nblk(ke, 256)), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(k_subs_run_len, dim3(nblk(ke, 256)), dim3(256), 0, s, *a);
+  }
+  hipLaunchKernelGGL(k_subs_commit, dim3(1), dim3(64), 0, s, *a);
   return hipGetLastError();
 }

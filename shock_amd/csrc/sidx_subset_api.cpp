@@ -78,6 +78,22 @@ std::string go_quote(const uint8_t *s, size_t n) {
   return q;
 }
 
+// Go's error text for a failing id (subset.go:203-223): txt, the first k bytes of its line, for Atoi's two
+std::string subset_error_text(u32 code, i64 v, i64 prev, const uint8_t *txt, u64 k) {
+  if (code == SUB_SYNTAX || code == SUB_RANGE)
+    return "strconv.Atoi: parsing " + go_quote(txt, k) + ": " + (code == SUB_SYNTAX ? "invalid syntax" : "value out of range");
+  char buf[256];
+  if (code == SUB_SORT)
+    snprintf(buf, sizeof buf,
+             "Subset indices must be numerically sorted and non-redundant, found value %lld after value %lld",
+             (long long)v, (long long)prev);
+  else if (code == SUB_EXIST)
+    snprintf(buf, sizeof buf, "Subset index: %lld does not exist in parent index file.", (long long)v);
+  else
+    snprintf(buf, sizeof buf, "Subset index could not read parent index file for part: %lld", (long long)v);
+  return buf;
+}
+
 // CreateSubsetNodeIndexes (subset.go:133-303) on the device, and optionally the subset node's
 // bytes (single.go:500-517): the id lines (the line index kernel), then every count -- the
 // non-blank ids, the first failing one, the accepted ids, the runs, oSize, the gathered bytes --
@@ -212,7 +228,8 @@ int subset_build(shockidx_ctx *c, const void *d_ids, uint64_t ids_len, const voi
   if (r) {
     if (int rc = d2h(c, &prev, cval + r - 1, res)) return rc;
   }
-  char buf[256];
+  uint8_t txt[200];
+  u64 k = 0;
   if (code == SUB_SYNTAX || code == SUB_RANGE) {
     u64 li = 0, ln[2];
     if (int rc = d2h(c, &li, cline + r, res)) return rc;
@@ -222,24 +239,13 @@ int subset_build(shockidx_ctx *c, const void *d_ids, uint64_t ids_len, const voi
     HIPCHK(hipStreamSynchronize(s), "sync");
     ln[0] = e2[0] + 1;  // (li == 0: ~0 + 1 = 0)
     ln[1] = e2[1] + 1 - ln[0];
-    const u64 k = ln[1] - 1 < 200 ? ln[1] - 1 : 200;  // enough for a 255-byte message
-    uint8_t txt[200];
+    k = ln[1] - 1 < 200 ? ln[1] - 1 : 200;  // enough for a 255-byte message
     if (k) {
       HIPCHK(hipMemcpyAsync(txt, (const uint8_t *)d_ids + ln[0], k, hipMemcpyDeviceToHost, s), "text copy");
       HIPCHK(hipStreamSynchronize(s), "sync");
     }
-    return set_msg(res, SHOCKIDX_EFORMAT, "strconv.Atoi: parsing " + go_quote(txt, k) + ": " +
-                                              (code == SUB_SYNTAX ? "invalid syntax" : "value out of range"));
   }
-  if (code == SUB_SORT)
-    snprintf(buf, sizeof buf,
-             "Subset indices must be numerically sorted and non-redundant, found value %lld after value %lld",
-             (long long)v, (long long)prev);
-  else if (code == SUB_EXIST)
-    snprintf(buf, sizeof buf, "Subset index: %lld does not exist in parent index file.", (long long)v);
-  else
-    snprintf(buf, sizeof buf, "Subset index could not read parent index file for part: %lld", (long long)v);
-  return set_msg(res, SHOCKIDX_EFORMAT, buf);
+  return set_msg(res, SHOCKIDX_EFORMAT, subset_error_text(code, v, prev, txt, k));
 }
 
 }  // namespace
@@ -323,6 +329,155 @@ int shockidx_create_subset_index(shockidx_ctx *c, const void *d_ids, uint64_t id
   res->runs = 0;
   if (rc == SHOCKIDX_EFORMAT) res->count = res->size = ~0ull;
   return rc;
+}
+
+}  // extern "C"
+
+// ---- the subset builders one slab of the id text at a time (subset.go:186-291) ----------------
+namespace sidx_host {
+
+namespace {
+u64 up256(u64 x) { return (x + 255) / 256 * 256; }
+// c->d_sends: the ends (a '\n' per byte at worst), the 1 KiB blocks' counts and bases, the scan's temp
+u64 subs_ends_bytes(u64 end, u64 ltmp) {
+  const u64 nb = (end + 1023) / 1024;
+  return up256(8 * (end + 2)) + up256(4 * nb) + up256(8 * nb) + up256(ltmp) + 256;
+}
+// c->d_sub: the control words and the per-line arrays for m lines
+u64 subs_line_bytes(u64 m, u64 scan_bytes) { return up256(8 * SL_WORDS) + 7 * up256(8 * (m + 1)) + up256(scan_bytes) + 256; }
+}  // namespace
+
+void subset_slab_ws_parts(u64 end, u64 *ends_bytes, u64 *line_bytes) {
+  size_t ltmp = 0, sb = 0;
+  (void)sidx_id_lines(nullptr, end, nullptr, nullptr, nullptr, nullptr, &ltmp, nullptr);
+  (void)sidx_scan_flags(nullptr, nullptr, end ? end : 1, nullptr, &sb, nullptr);  // (a line per byte at worst)
+  *ends_bytes = subs_ends_bytes(end, ltmp);
+  *line_bytes = subs_line_bytes(end, sb);
+}
+u64 subset_slab_ws_bytes(u64 end) {
+  u64 a = 0, b = 0;
+  subset_slab_ws_parts(end, &a, &b);
+  return a + b;
+}
+
+u64 subset_whole_bytes(u64 ids_size, u64 parent_bytes) {
+  // a bound: the two files, subset_build's ends (8 bytes per text byte), its per-line workspace (64
+  // bytes a line, a line per byte when they are all blank) and both tables (a row per two bytes);
+  // an eighth on top for DevBuf::ensure's growth
+  const u64 b = ids_size + parent_bytes + 8 * (ids_size + 2) + 64 * (ids_size + 8) + 32 * (ids_size / 2 + 4096) +
+                (1ull << 20);
+  return b + b / 8;
+}
+
+}  // namespace sidx_host
+
+extern "C" {
+
+uint64_t shockidx_subset_carry_bytes(void) { return sizeof(SubCarry); }
+
+// One slab of CreateSubsetNodeIndexes / CreateSubsetIndex (subset.go:186-291 with the loop's state,
+// :161-176, in the device carry).  The host waits three times: for the window's line count, for the
+// plan (where the call stops, what it writes) and for the commit.
+int shockidx_subset_slab_device(shockidx_ctx *c, const shockidx_slab *slab, uint64_t ids_size, const void *d_parent,
+                                uint64_t prow0, uint64_t prows, uint64_t parent_count, int64_t ilength, int want_runs,
+                                void *d_carry, void *d_rows, uint64_t rows_cap, void *d_runs, uint64_t runs_cap,
+                                shockidx_subset_slab_result *res) {
+  shockidx_subset_slab_result tmp;
+  if (!res) res = &tmp;
+  reset_result(res);
+  if (!c || !slab || !d_carry || (!d_rows && rows_cap) || (!d_runs && runs_cap) || (!d_parent && prows))
+    return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+  const shockidx_slab &b = *slab;
+  const bool first = b.base == 0, last = b.base + b.n == ids_size;
+  if (b.end < b.n || b.base > ids_size || b.end > ids_size - b.base || (!b.n && ids_size) ||
+      (b.n && (!b.d_data || ((uintptr_t)b.d_data & 15))) || (b.is_first != 0) != first || (b.is_last != 0) != last ||
+      b.front < (b.base < 16 ? b.base : 16) || b.front > b.base || ((uintptr_t)d_carry & 7) ||
+      ((uintptr_t)d_parent & 15) || ((uintptr_t)d_rows & 15) || ((uintptr_t)d_runs & 15) ||
+      prow0 > parent_count || prows > parent_count - prow0)
+    return set_msg(res, SHOCKIDX_EINVAL, "invalid argument");
+  const double t0 = now_ms();
+  HIPCHK(hipSetDevice(c->device), "hipSetDevice");
+  hipStream_t s = c->stream;
+  const u64 end = b.end, nb = (end + 1023) / 1024;
+  size_t ltmp = 0;
+  HIPCHK(sidx_id_lines(nullptr, end, nullptr, nullptr, nullptr, nullptr, &ltmp, s), "scan size");
+  if (int rc = c->d_sends.ensure(subs_ends_bytes(end, ltmp), res)) return rc;
+  Carver lc{c->d_sends};
+  u64 *ends = lc.take<u64>(end + 2);
+  u32 *cnt = lc.take<u32>(nb);
+  u64 *lbase = lc.take<u64>(nb);
+  void *ltmp_p = lc.take<uint8_t>(ltmp);
+  HIPCHK(hipEventRecord(c->ek0, s), "event");
+  u64 m = 0;
+  if (nb) {
+    HIPCHK(sidx_id_lines((const uint8_t *)b.d_data, end, cnt, lbase, ends, ltmp_p, &ltmp, s), "id lines");
+    u64 b_last = 0;
+    u32 c_last = 0;
+    HIPCHK(hipMemcpyAsync(&b_last, lbase + nb - 1, 8, hipMemcpyDeviceToHost, s), "line count copy");
+    HIPCHK(hipMemcpyAsync(&c_last, cnt + nb - 1, 4, hipMemcpyDeviceToHost, s), "line count copy");
+    HIPCHK(hipStreamSynchronize(s), "line count sync");
+    m = b_last + c_last;
+  }
+  size_t scan_bytes = 0;
+  HIPCHK(sidx_scan_flags(nullptr, nullptr, m ? m : 1, nullptr, &scan_bytes, s), "scan size");
+  if (int rc = c->d_sub.ensure(subs_line_bytes(m, scan_bytes), res)) return rc;
+  Carver cv{c->d_sub};
+  SubSlabArgs a;
+  memset(&a, 0, sizeof a);
+  a.text = (const uint8_t *)b.d_data;
+  a.n = b.n; a.end = end; a.front = b.front; a.base = b.base; a.ids_size = ids_size;
+  a.is_first = first; a.is_last = last; a.want_runs = want_runs != 0;
+  a.parent = (const u64 *)d_parent; a.prow0 = prow0; a.prows = prows; a.parent_count = parent_count;
+  a.ilength = ilength;
+  a.carry = (SubCarry *)d_carry;
+  a.rows = (u64 *)d_rows; a.rows_cap = rows_cap; a.runs = (u64 *)d_runs; a.runs_cap = runs_cap;
+  a.m = m;
+  a.ends = ends;
+  a.ctl = cv.take<u64>(SL_WORDS);
+  a.keep = cv.take<u32>(2 * (m + 1));
+  a.val = cv.take<i64>(m + 1);
+  a.st = cv.take<u32>(2 * (m + 1));
+  a.rank = cv.take<u64>(m + 1);
+  a.cval = cv.take<i64>(m + 1);
+  a.cst = cv.take<u32>(2 * (m + 1));
+  a.cline = cv.take<u64>(m + 1);
+  void *scan_tmp = cv.take<uint8_t>(scan_bytes);
+  HIPCHK(sidx_subs_plan(&a, scan_tmp, &scan_bytes, s), "subset slab launch");
+  u64 w[SL_WORDS];
+  HIPCHK(hipMemcpyAsync(w, a.ctl, sizeof w, hipMemcpyDeviceToHost, s), "control copy");
+  HIPCHK(hipStreamSynchronize(s), "subset slab sync");
+  if (w[SL_FLAGS])
+    return set_msg(res, SHOCKIDX_EINVAL, "the carry does not allow this slab: its walk has ended or not begun, or its next line lies outside the slab");
+  const u64 ke = w[SL_KE], nruns_call = w[SL_NCLOSED] + w[SL_FINAL];
+  res->rows = ke;
+  res->runs = nruns_call;
+  if (ke > rows_cap) return set_msg(res, SHOCKIDX_ESPACE, "row capacity too small");
+  if (nruns_call > runs_cap) return set_msg(res, SHOCKIDX_ESPACE, "run capacity too small");
+  HIPCHK(sidx_subs_commit(&a, ke, w[SL_NCLOSED], s), "subset commit launch");
+  HIPCHK(hipEventRecord(c->ek1, s), "event");
+  HIPCHK(hipStreamSynchronize(s), "subset slab sync");
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, c->ek0, c->ek1);
+  res->kernel_ms = ms;
+  res->count = w[SL_COUNT];
+  res->nruns = w[SL_NRUNS];
+  res->size = w[SL_TOTSIZE];
+  res->stop = (int32_t)w[SL_STOP];
+  res->next_off = w[SL_NEXT_OFF];
+  res->next_id = (int64_t)w[SL_NEXT_ID];
+  res->total_ms = now_ms() - t0;
+  const u32 code = (u32)w[SL_CODE];
+  if (!code) return SHOCKIDX_OK;
+  uint8_t txt[200];
+  u64 k = 0;
+  if (code == SUB_SYNTAX || code == SUB_RANGE) {
+    k = w[SL_ERR_LEN] < 200 ? w[SL_ERR_LEN] : 200;  // enough for a 255-byte message
+    if (k) {
+      HIPCHK(hipMemcpyAsync(txt, (const uint8_t *)b.d_data + w[SL_ERR_OFF], k, hipMemcpyDeviceToHost, s), "text copy");
+      HIPCHK(hipStreamSynchronize(s), "sync");
+    }
+  }
+  return set_msg(res, SHOCKIDX_EFORMAT, subset_error_text(code, (i64)w[SL_ERR_V], (i64)w[SL_ERR_PREV], txt, k));
 }
 
 }  // extern "C"

@@ -22,6 +22,27 @@ from .core import write_idx
 from .indexer import PATH_DATA, ShockIndexError, context
 
 
+def _is_path(f) -> bool:
+    return isinstance(f, (str, bytes, os.PathLike))
+
+
+def _create_from_files(ids, par_fd: int, ilength: int, cofile, ofile: str):
+    """shockidx_subset_create over the id file and the open parent index (closed here): the library reads
+    them, walks them in slabs when they do not fit the device budget, and writes and renames the tables
+    itself."""
+    try:
+        ids_fd = os.open(ids, os.O_RDONLY)
+        try:
+            tmpdir = os.path.join(PATH_DATA, "temp")
+            os.makedirs(tmpdir, exist_ok=True)
+            return context().subset_create(ids_fd, os.fstat(ids_fd).st_size, par_fd, os.fstat(par_fd).st_size,
+                                           int(ilength), tmpdir, cofile, ofile)
+        finally:
+            os.close(ids_fd)
+    finally:
+        os.close(par_fd)
+
+
 def _read(f) -> bytes:
     if hasattr(f, "read"):
         return f.read()
@@ -34,6 +55,9 @@ def CreateSubsetNodeIndexes(ids, cofile: str, ofile: str, ifile: str, iformat: s
     if iformat != "array":  # subset.go:298-300
         return 0, 0, 0, ShockIndexError(
             b"Subset node does not currently support the format of your parent index: " + iformat.encode())
+    if _is_path(ids) and _is_path(ifile):
+        r = _create_from_files(ids, os.open(ifile, os.O_RDONLY), ilength, cofile, ofile)
+        return r.runs, r.count, r.size, (None if r.ok else ShockIndexError(r.err))
     text = _read(ids)
     raw = _read(ifile)
     parent = np.frombuffer(raw[: len(raw) // 16 * 16], dtype="<u8").reshape(-1, 2)  # ReadAt of whole rows
@@ -53,6 +77,15 @@ def CreateSubsetIndex(ids, oifile: str, ifile: str, iformat: str, ilength: int):
     if iformat != "array":  # subset.go:125-127
         return -1, -1, ShockIndexError(
             b"Subset index does not currently support the format of your parent index: " + iformat.encode())
+    if _is_path(ids) and _is_path(ifile):
+        try:
+            par_fd = os.open(ifile, os.O_RDONLY)  # os.Open(ifile) (:40-43)
+        except OSError as e:
+            return -1, -1, ShockIndexError(str(e).encode())
+        r = _create_from_files(ids, par_fd, ilength, None, oifile)
+        if not r.ok:
+            return -1, -1, ShockIndexError(r.err)
+        return int(r.count), int(r.size), None
     try:
         raw = _read(ifile)  # os.Open(ifile) (:40-43)
     except OSError as e:
