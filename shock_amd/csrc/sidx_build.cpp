@@ -98,6 +98,13 @@ static bool ws_contig(int bit) {
 void trim_workspace(shockidx_ctx *c, u64 keep) {
   if (c->bufs.trim(keep, [c] { (void)hipStreamSynchronize(c->stream); })) c->last_spans = false;
 }
+int exact_workspace(shockidx_ctx *c, std::initializer_list<BufSet::Want> want, Err res) {
+  auto quiesce = [c] {  // (called when the trim acts, as in trim_workspace)
+    (void)hipStreamSynchronize(c->stream);
+    c->last_spans = false;
+  };
+  return c->bufs.exact(want, quiesce, res);
+}
 
 // test hook: every status word published (INC) with the next build's epoch and payload 0, on
 // the build stream -- the stale look-back words a recycled allocation could hold

@@ -2,7 +2,7 @@
 // entry points (device, host memory, file descriptor), Create and the .idx writer with the
 // reference's temp-file + rename protocol (shock-server/node/file/index/record.go:35-41,65-87),
 // device memory, the multi-GPU slab and communicator entry points, format detection.  The work
-// is in sidx_build.cpp (one index build, staging) and sidx_pipeline.cpp (the slab pipelines);
+// is in sidx_build.cpp (one index build, staging), sidx_pipeline.cpp and sidx_walks.cpp (the slab walks);
 // chunkrecord, subset and filter entry points have files of their own.  No index computation
 // happens on the host: without a usable GPU every entry point fails with SHOCKIDX_EHIP.
 #include <errno.h>
@@ -25,7 +25,7 @@
 #include "sidx_subset.hpp"
 #include "sidx_launch.hpp"
 #include "sidx_slabwalk.hpp"
-#include "sidx_host.hpp"
+#include "sidx_walk.hpp"
 
 using namespace sidx;
 using namespace sidx_host;
@@ -431,20 +431,9 @@ int subset_whole(shockidx_ctx *c, int ids_fd, u64 n, int parent_fd, u64 parent_b
   reset_result(&r1);
   if (int rc = stage_fd(c, ids_fd, 0, n, s, &r1)) return forward_error(res, r1, rc);
   if (int rc = c->d_spar.ensure(16 * parent_count + 16, res)) return rc;
-  for (int i = 0; i < 2; ++i)
-    if (!c->h_rows[i]) HIPCHK(hipHostMalloc(&c->h_rows[i], STAGE_BYTES, 0), "hipHostMalloc(rows)");
-  for (u64 done = 0, total = 16 * parent_count; done < total;) {
-    const u64 k = total - done < STAGE_BYTES ? total - done : STAGE_BYTES;
-    for (u64 got = 0; got < k;) {
-      const ssize_t r = pread(parent_fd, c->h_rows[1] + got, k - got, (off_t)(done + got));
-      if (r < 0 && errno == EINTR) continue;
-      if (r <= 0) return set_msg(res, SHOCKIDX_EIO, r < 0 ? strerror(errno) : "unexpected end of file");
-      got += (u64)r;
-    }
-    HIPCHK(hipMemcpyAsync(c->d_spar + done, c->h_rows[1], k, hipMemcpyHostToDevice, s), "parent copy");
-    HIPCHK(hipStreamSynchronize(s), "parent copy");
-    done += k;
-  }
+  if (int rc = walk_prereqs(c, res)) return rc;
+  if (int rc = file_to_device(c, parent_fd, 0, 16 * parent_count, c->d_spar, "", "unexpected end of file", "parent copy", res))
+    return rc;
   u64 rows_cap = n / 8 + 4096, runs_cap = want_runs ? rows_cap : 0;
   int rc = 0;
   for (int attempt = 0;; ++attempt) {
@@ -459,18 +448,9 @@ int subset_whole(shockidx_ctx *c, int ids_fd, u64 n, int parent_fd, u64 parent_b
   }
   if (rc != SHOCKIDX_OK && rc != SHOCKIDX_EFORMAT) return rc;
   const shockidx_subset_result keep = *res;
-  const u64 per = STAGE_BYTES / 16;
-  for (int t = 0; t < (want_runs ? 2 : 1); ++t) {
-    const u64 m = t ? keep.runs : keep.count;
-    const u64 *d = t ? (const u64 *)c->d_sruns.as<u64>() : (const u64 *)c->d_cola.as<u64>();
-    for (u64 done = 0; done < m;) {
-      const u64 k = m - done < per ? m - done : per;
-      HIPCHK(hipMemcpyAsync(c->h_rows[0], d + 2 * done, k * 16, hipMemcpyDeviceToHost, s), "rows copy");
-      HIPCHK(hipStreamSynchronize(s), "rows copy");
-      if (int e = (t ? sinks.runs : sinks.rows)->put(c->h_rows[0], done, k, res)) return e;
-      done += k;
-    }
-  }
+  if (int e = drain_rows(c, c->d_cola.as<u64>(), keep.count, 0, *sinks.rows, nullptr, nullptr, res)) return e;
+  if (want_runs)
+    if (int e = drain_rows(c, c->d_sruns.as<u64>(), keep.runs, 0, *sinks.runs, nullptr, nullptr, res)) return e;
   *res = keep;
   return rc;
 }

@@ -1,5 +1,5 @@
 // sidx_chunkwalk.hpp -- the arithmetic of the chunkrecord index's slab walk
-// (shockidx_chunkrecord_fd_walk, sidx_pipeline.cpp; the slab step: shockidx_chunkrecord_slab_device)
+// (shockidx_chunkrecord_fd_walk, sidx_walks.cpp; the slab step: shockidx_chunkrecord_slab_device)
 // that needs no device: where slab k lies in the file and in its slot, how many rows a slab can
 // emit, what one slab's workspace may grow to, how large a slab a device budget allows, and the
 // precondition on a carry that enters a slab.  No HIP calls, so tests/host/chunkwalk_test.cpp
@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "sidx_common.hpp"
+#include "sidx_slabwalk.hpp"  // largest_slab
 
 namespace sidx {
 
@@ -103,13 +104,7 @@ inline u64 chunkwalk_footprint(u64 S, u64 chunk, const ChunkWalkDev &dv) {
 // the budget is under CHUNKWALK_MIN_BUDGET, or leaves no room for a slab.
 inline u64 chunkwalk_slab_bytes(u64 budget, u64 chunk, const ChunkWalkDev &dv) {
   if (budget < CHUNKWALK_MIN_BUDGET) return 0;
-  u64 lo = 0, hi = CHUNKWALK_MAX_SLAB / CHUNKWALK_ALIGN;  // (the footprint grows with S: bisect on S / ALIGN)
-  while (lo < hi) {
-    const u64 mid = (lo + hi + 1) / 2;
-    if (chunkwalk_footprint(mid * CHUNKWALK_ALIGN, chunk, dv) <= budget) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo * CHUNKWALK_ALIGN;
+  return largest_slab(CHUNKWALK_ALIGN, CHUNKWALK_MAX_SLAB, [&](u64 S) { return chunkwalk_footprint(S, chunk, dv) <= budget; });
 }
 
 // What the whole-node build of an n-byte node holds at its peak (shockidx_chunkrecord_fd without the

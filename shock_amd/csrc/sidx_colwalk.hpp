@@ -1,5 +1,5 @@
 // sidx_colwalk.hpp -- the arithmetic and decisions of the column index's slab walk
-// (shockidx_column_fd_walk, sidx_pipeline.cpp) that need no device: how large a slab a device
+// (shockidx_column_fd_walk, sidx_walks.cpp) that need no device: how large a slab a device
 // budget allows, where a slab lies in its slot, what a slab's result means for the walk (the one
 // retry rule), and the row cursor.  No HIP calls, so tests/host/colwalk_test.cpp exercises every
 // piece on the CPU.
@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "sidx_common.hpp"
+#include "sidx_slabwalk.hpp"  // largest_slab
 
 namespace sidx {
 
@@ -37,13 +38,7 @@ u64 colwalk_footprint(u64 S, u64 halo, u64 carry_bytes, WsBytes ws) {
 template <class WsBytes>
 u64 colwalk_slab_bytes(u64 budget, u64 halo, u64 carry_bytes, WsBytes ws) {
   if (budget < COLWALK_MIN_BUDGET) return 0;
-  u64 lo = 0, hi = (1ull << 30) / COLWALK_ALIGN;  // (the footprint grows with S: bisect on S / ALIGN)
-  while (lo < hi) {
-    const u64 mid = (lo + hi + 1) / 2;
-    if (colwalk_footprint(mid * COLWALK_ALIGN, halo, carry_bytes, ws) <= budget) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo * COLWALK_ALIGN;
+  return largest_slab(COLWALK_ALIGN, 1ull << 30, [&](u64 S) { return colwalk_footprint(S, halo, carry_bytes, ws) <= budget; });
 }
 
 // Slab [lo, lo + n) of a size-byte file in its slot: `front` bytes before it and `end` readable

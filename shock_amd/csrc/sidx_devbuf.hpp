@@ -9,6 +9,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <string>
 
 #include "../../include/shockidx.h"
@@ -136,6 +137,23 @@ class BufSet {
     drop(BufClass::Large);
     if (keep == 0 || bytes() > keep) drop(BufClass::Tile);
     return true;
+  }
+  // An exact-size workspace: each listed buffer holds exactly its n elements afterwards.  All do
+  // already: nothing is trimmed or allocated.  Else everything goes first (trim to 0: the caches
+  // of other builds), then each is allocated in list order; the first failure is returned, the
+  // ones before it held, it and the ones after it empty.
+  struct Want {
+    DevBufBase *buf;
+    uint64_t n;
+  };
+  template <class Quiesce> int exact(std::initializer_list<Want> want, Quiesce quiesce, Err res) {
+    bool held = true;
+    for (const Want &w : want) held = held && w.buf->cap == w.n;
+    if (held) return 0;
+    trim(0, quiesce);
+    for (const Want &w : want)
+      if (int rc = w.buf->exact(w.n, res)) return rc;
+    return 0;
   }
 
  private:

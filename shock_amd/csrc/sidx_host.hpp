@@ -1,7 +1,8 @@
 // sidx_host.hpp -- the host side of libshockidx as its translation units see each other: the
 // context and its device caches (sidx_devbuf.hpp), the error helpers, and the functions of
-// sidx_build.cpp (workspaces, one index pass, staging, copy-out) and sidx_pipeline.cpp (the slab
-// pipelines) that the entry points call.
+// sidx_build.cpp (workspaces, one index pass, staging, copy-out), sidx_pipeline.cpp (the record
+// slab pipelines) and sidx_walks.cpp (the column, subset and chunkrecord walks) that the entry
+// points call.  What those two share among themselves is in sidx_walk.hpp.
 // Internal: not part of the C ABI (include/shockidx.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -216,6 +217,9 @@ inline sidx::u64 workspace_bytes(const shockidx_ctx *c) { return c->bufs.bytes()
 // free the large caches when the total is over `keep` (they regrow on demand); the tile block
 // goes only with keep = 0, or when the rest is still over keep (BufSet::trim)
 void trim_workspace(shockidx_ctx *c, sidx::u64 keep);
+// the exact-size workspace of a slab walk (BufSet::exact): nothing happens when every size matches,
+// else a trim to 0 and each buffer allocated in list order
+int exact_workspace(shockidx_ctx *c, std::initializer_list<BufSet::Want> want, Err res);
 // trims the caches to the context's cap when a host-facing call returns
 struct TrimGuard {
   shockidx_ctx *c;
@@ -302,7 +306,7 @@ struct FileSink : RowSink {  // the .idx temp file: rows are {u64 off, u64 len} 
   int fd = -1;
   int put(const uint8_t *src, sidx::u64 first, sidx::u64 nrows, Err res) override;
 };
-// ---- the column index in slabs (sidx_column_api.cpp, sidx_pipeline.cpp) ------------------------
+// ---- the column index in slabs (sidx_column_api.cpp, sidx_walks.cpp) ---------------------------
 // One slab of the column slab pass: n owned bytes at d (16-byte aligned), `end` readable from d,
 // `front` before it, d[0] at file offset base.  ws: sidx_col_tile_bytes(tiles of n, at least 1)
 // bytes.  Returns like shockidx_column_slab_device; waits for the stream.
@@ -321,7 +325,7 @@ sidx::u64 column_whole_bytes(sidx::u64 n);
 int column_fd_walk(shockidx_ctx *c, int fd, sidx::u64 n, sidx::u32 column, sidx::u64 S, sidx::u64 halo, RowSink &sink,
                    shockidx_result *res);
 
-// ---- the chunkrecord index in slabs (sidx_chunk_api.cpp, sidx_pipeline.cpp) --------------------
+// ---- the chunkrecord index in slabs (sidx_chunk_api.cpp, sidx_walks.cpp) -----------------------
 // One slab of chunkrecord over the view v (sidx_common.hpp) with the carry on the device; first:
 // the carry is initialised with fmt (later slabs take the format from it).  Rows at file offsets
 // into rows[0..row_cap).  Returns like shockidx_chunkrecord_slab_device; waits for the stream.
@@ -337,7 +341,7 @@ sidx::ChunkWalkDev chunk_walk_dev(shockidx_ctx *c, sidx::u64 len);
 int chunk_fd_walk(shockidx_ctx *c, int fd, sidx::u64 n, int fmt, sidx::u64 chunk, sidx::u64 S, RowSink &sink,
                   shockidx_result *res);
 
-// ---- the subset indexes in slabs (sidx_subset_api.cpp, sidx_pipeline.cpp) ----------------------
+// ---- the subset indexes in slabs (sidx_subset_api.cpp, sidx_walks.cpp) -------------------------
 // device bytes one slab call over a window of `end` readable bytes takes from the context's caches
 // (c->d_sends, c->d_sub): 8 bytes per text byte for the line ends, the per-line arrays, the scans
 sidx::u64 subset_slab_ws_bytes(sidx::u64 end);

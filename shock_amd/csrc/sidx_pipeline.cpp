@@ -35,11 +35,13 @@
 //
 // The host-memory pipeline (build_host_pipelined, FASTQ bodies in pinned memory) is the same walk
 // over the whole layout without a second thread: the copies are all issued up front.
+//
+// The walks that carry their state on the device (column, subset, chunkrecord) are in
+// sidx_walks.cpp; sidx_walk.hpp has what they share with these.
 #include <errno.h>
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/mman.h>
 #include <unistd.h>
 
 #include <condition_variable>
@@ -51,11 +53,8 @@
 #include "../../include/shockidx.h"
 #include "sidx_common.hpp"
 #include "sidx_slabwalk.hpp"
-#include "sidx_colwalk.hpp"
-#include "sidx_chunkwalk.hpp"
-#include "sidx_subwalk.hpp"
 #include "sidx_launch.hpp"
-#include "sidx_host.hpp"
+#include "sidx_walk.hpp"
 
 using namespace sidx;
 
@@ -102,29 +101,6 @@ int FileSink::put(const uint8_t *src, u64 first, u64 nrows, Err res) {
 }
 
 namespace {
-
-// the slab builds' end-of-build invariants (never expected: a violation is an internal error,
-// not a short table)
-const char *const SLAB_SEAM_MSG = "internal error: a slab's first row does not start where the previous slab's rows end";
-const char *const SLAB_END_MSG = "internal error: the rows do not end at the end of the file";
-
-// One arrival event per slab, recorded on the copy stream.  Destroyed only once the copy stream
-// has drained: declare it before whatever issues copies, so that it is destroyed after it.
-struct SlabEvents {
-  std::vector<hipEvent_t> ev;
-  hipStream_t copy_stream;
-  SlabEvents(u64 K, hipStream_t cs) : ev(K, nullptr), copy_stream(cs) {}
-  hipError_t create() {
-    for (auto &e : ev)
-      if (hipError_t rc = hipEventCreateWithFlags(&e, hipEventDisableTiming)) return rc;
-    return hipSuccess;
-  }
-  ~SlabEvents() {
-    (void)hipStreamSynchronize(copy_stream);
-    for (auto e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
 
 // Slab k of the layout, at d_slab, indexed into the context's rows from row `row_off` on (room
 // for row_cap rows) with the previous slab's end state.  grow: a slab with more rows than its
@@ -231,135 +207,15 @@ struct Walk {
   uint8_t *slab_ptr(u64 k) const { return lay.ring ? c->d_slot[k & 1] + lay.front(k) : c->d_in + lay.lo(k); }
 };
 
-// Node bytes to device memory on the copy stream.  (a) DMA straight out of the page cache: the
-// file mapped read-only and pinned 256 MiB at a time (hipHostRegister of page-cached pages runs at
-// ~160 GB/s, ahead of PCIe), so the bytes cross the host's memory once instead of being copied
-// into pinned staging first (tools/probes/regprobe.cpp: register 6.7 ms + H2D 18.7 ms per GiB).
-// Chunks stay pinned until the copy stream drains (unpinning behind the DMA cost a quarter of the
-// rate, profiles/r04/e2e_fd_page_cache_dma.txt) -- unless the process-wide pin budget runs out,
-// when the ring unpins the chunks behind its current slab.  (b) When the file does not map or its
-// pages do not pin: the copy threads pread it into the two pinned staging buffers.
-// Lifetime: the copy stream must have drained before a chunk is unpinned or the file unmapped, so
-// the destructor drains it first (drain() does, and reports the error); and the slabs' arrival
-// events outlive this object (SlabEvents is declared before it).
-class PageCacheSource {
- public:
-  PageCacheSource(shockidx_ctx *c, int fd, u64 base, u64 n, Err res)
-      : c_(c), res_(res), a0_(base & ~4095ull), lead_(base - a0_), mn_(lead_ + n),
-        maplen_((size_t)((mn_ + 4095) & ~4095ull)), pinned_((mn_ + CH - 1) / CH, 0), fill_{fd, res, c->pool} {
-    if (!getenv("SHOCKIDX_NO_MMAP_DMA")) {
-      void *mp = mmap(nullptr, maplen_, PROT_READ, MAP_SHARED, fd, (off_t)a0_);
-      if (mp != MAP_FAILED) map_ = (uint8_t *)mp;
-    }
-    pin_ok_ = map_ != nullptr;
-  }
-  ~PageCacheSource() {
-    if (!drained_) (void)hipStreamSynchronize(c_->s_copy);
-    for (u64 j = 0; j < pinned_.size(); ++j) unpin(j);
-    if (map_) munmap(map_, maplen_);
-  }
-  PageCacheSource(const PageCacheSource &) = delete;
-  // every copy issued so far has landed
-  hipError_t drain() {
-    drained_ = true;
-    return hipStreamSynchronize(c_->s_copy);
-  }
-  // node bytes [a, b) to device address dst: pinned chunks, else staging.  keep_from: the chunks
-  // wholly before this node byte may be unpinned when the pin budget runs out
-  int copy_range(uint8_t *dst, u64 a, u64 b, u64 keep_from) {
-    const Err res = res_;
-    a += lead_;  // (map coordinates from here: file offset a0 + x)
-    b += lead_;
-    keep_from += lead_;
-    while (a < b) {
-      const u64 j = a / CH, ce = (j + 1) * CH < b ? (j + 1) * CH : b;
-      if (pin(j, keep_from)) {
-        if (hipError_t e = hipMemcpyAsync(dst, map_ + a, ce - a, hipMemcpyHostToDevice, c_->s_copy)) return set_hip(res, e, "page-cache DMA");
-        dst += ce - a;
-        a = ce;
-        continue;
-      }
-      const size_t k = ce - a < STAGE_BYTES ? (size_t)(ce - a) : STAGE_BYTES;
-      HIPCHK(hipEventSynchronize(c_->stage_ev[stage_i_]), "stage wait");  // buffer free again
-      if (int rc = fill_(c_->h_stage[stage_i_], a0_ + a, k)) return rc;
-      hipError_t e;
-      if ((e = hipMemcpyAsync(dst, c_->h_stage[stage_i_], k, hipMemcpyHostToDevice, c_->s_copy)) != hipSuccess ||
-          (e = hipEventRecord(c_->stage_ev[stage_i_], c_->s_copy)) != hipSuccess)
-        return set_hip(res, e, "H2D");
-      stage_i_ ^= 1;
-      dst += k;
-      a += k;
-    }
-    return 0;
-  }
-
- private:
-  static constexpr u64 CH = 256ull << 20;  // (chunks in map coordinates)
-  size_t chunk_len(u64 j) const { return (size_t)((((j * CH + CH < mn_ ? j * CH + CH : mn_) + 4095) & ~4095ull) - j * CH); }
-  void unpin(u64 j) {
-    if (!pinned_[j]) return;
-    (void)hipHostUnregister(map_ + j * CH);
-    pin_release(pinned_[j]);
-    pinned_[j] = 0;
-  }
-  // pin chunk j (reserving its bytes); false: it does not pin (the caller stages instead)
-  bool pin(u64 j, u64 keep_from) {
-    if (pinned_[j]) return true;
-    if (!pin_ok_) return false;
-    const u64 len = chunk_len(j);
-    if (!pin_reserve(len)) {
-      // over the process-wide budget: unpin the chunks wholly before keep_from (their copies
-      // must have landed first), then try once more
-      bool any = false;
-      for (u64 i = 0; i < j && (i + 1) * CH <= keep_from; ++i) any |= pinned_[i] != 0;
-      if (!any || hipStreamSynchronize(c_->s_copy) != hipSuccess) return false;
-      for (u64 i = 0; i < j && (i + 1) * CH <= keep_from; ++i) unpin(i);
-      if (!pin_reserve(len)) return false;
-    }
-    if (hipHostRegister(map_ + j * CH, len, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      pin_release(len);
-      pin_ok_ = false;
-      return false;
-    }
-    pinned_[j] = len;
-    return true;
-  }
-  shockidx_ctx *c_;
-  Err res_;
-  const u64 a0_, lead_, mn_;  // the file from the page below base: node byte a is map[lead + a]
-  const size_t maplen_;
-  uint8_t *map_ = nullptr;
-  std::vector<u64> pinned_;  // bytes registered (and reserved) per chunk
-  bool pin_ok_ = false;      // chunks still pin (else the staging path from here on)
-  bool drained_ = false;
-  int stage_i_ = 0;
-  PreadFill fill_;
-};
-
-// A slab's owned rows (device rows [0, owned)) D2H through the two pinned row buffers into the
-// sink: chunk j + 1's DMA overlaps chunk j's sink.  0, or the library code (message in o.cres).
-int rows_to_sink(Walk &w, WalkResult &o, u64 owned) {
-  shockidx_ctx *c = w.c;
-  const double td = now_ms();
-  const u64 per = STAGE_BYTES / 16;
-  u64 done_rows = 0;
-  int b = 0;
-  while (done_rows < owned) {
-    const u64 m = owned - done_rows < per ? owned - done_rows : per;
-    if (hipMemcpyAsync(c->h_rows[b], c->d_rows + 2 * done_rows, m * 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)
-      return set_msg(&o.cres, SHOCKIDX_EHIP, "rows copy");
-    // the slab's rows continue the table (record.go:51-83): its first row starts where the
-    // previous slab's last row ended
-    const u64 at = o.cur.total;
-    if (!o.cur.accept((const u64 *)c->h_rows[b], m, done_rows == 0)) return set_msg(&o.cres, SHOCKIDX_EINTERNAL, SLAB_SEAM_MSG);
-    if (int r = w.sink.put(c->h_rows[b], at, m, &o.cres)) return r;
-    done_rows += m;
-    b ^= 1;
-  }
-  o.t_d2h += now_ms() - td;
-  return 0;
+// The table's next m rows (device rows [0, m), `shift` added to their offsets) into the sink.
+// They continue the table (record.go:51-83): the first starts where the last row before them
+// ended.  0, or the library code (message in res).
+int rows_to_sink(Walk &w, WalkResult &o, u64 m, u64 shift, Err res) {
+  auto accept = [&](u64 *rows, u64 k, u64 done) {
+    for (u64 i = 0; shift && i < k; ++i) rows[2 * i] += shift;
+    return o.cur.accept(rows, k, done == 0) ? 0 : set_msg(res, SHOCKIDX_EINTERNAL, SLAB_SEAM_MSG);
+  };
+  return drain_rows(w.c, w.c->d_rows, m, o.cur.total, w.sink, accept, &o.t_d2h, res);
 }
 
 // The index thread: slab k after its bytes (+ halo) have arrived.
@@ -390,7 +246,7 @@ void index_slabs(Walk &w, WalkResult &o) {
     o.cres.index_ms += r2.index_ms;
     const SlabOutcome oc = classify(rc, dr, row_base, lay.last(k), lay.ring);
     if (oc == SlabOutcome::FallBack) { o.end = WalkEnd::FallBack; return; }
-    if (int e = rows_to_sink(w, o, dr.count - row_base)) return o.fail(e);
+    if (int e = rows_to_sink(w, o, dr.count - row_base, 0, &o.cres)) return o.fail(e);
     state = dr.state_out;
     if (oc == SlabOutcome::GoError) {
       o.err_dr = dr;
@@ -446,17 +302,9 @@ int transfer(Walk &w, WalkResult &o, Err res) {
   return prc;
 }
 
-// count, format, path and the times of a walk that ends here
-void finish_walk(shockidx_result *res, int kfmt, u64 total, u32 path, const shockidx_result &cres, double t_d2h,
-                 double t0) {
-  res->count = total;
-  res->format = kfmt == F_LINE ? SHOCKIDX_FMT_LINE : kfmt;
-  res->path = path;
-  res->kernel_ms = cres.kernel_ms;
-  res->index_ms = cres.index_ms;
-  res->d2h_ms = t_d2h;
-  res->total_ms = now_ms() - t0;
-  res->h2d_ms = res->total_ms - t_d2h - res->kernel_ms;  // the rest is waiting for the PCIe stream
+// the record walk ends here: its count and the times its index thread carried
+void finish_record_walk(shockidx_result *res, int kfmt, u32 path, const WalkResult &o, double t0) {
+  finish_walk(res, kfmt, o.cur.total, path, o.cres.kernel_ms, o.cres.index_ms, o.t_d2h, t0);
 }
 
 // Ring, no progress (a record the walk cannot close from its own start): the rest of the file
@@ -475,22 +323,10 @@ int one_pass_rest(Walk &w, WalkResult &o, shockidx_result *res, double t0) {
   const int sfmt = o.cur.total ? (o.kfmt == F_LINE ? SHOCKIDX_FMT_AUTO : o.kfmt) : w.fmt;
   const int rc = build_resident(c, c->d_in, end - r, w.kind, sfmt, s, &r3);
   if (rc < 0) return forward_error(res, r3, rc);
-  const double td = now_ms();
-  const u64 per = STAGE_BYTES / 16;
-  for (u64 d = 0; d < r3.count;) {
-    const u64 m = r3.count - d < per ? r3.count - d : per;
-    HIPCHK(hipMemcpyAsync(c->h_rows[0], c->d_rows + 2 * d, m * 16, hipMemcpyDeviceToHost, s), "rows copy");
-    HIPCHK(hipStreamSynchronize(s), "rows copy");
-    u64 *hr = (u64 *)c->h_rows[0];
-    for (u64 i = 0; i < m; ++i) hr[2 * i] += r;
-    const u64 at = o.cur.total;
-    if (!o.cur.accept(hr, m, d == 0)) return set_msg(res, SHOCKIDX_EINTERNAL, SLAB_SEAM_MSG);
-    if (int e = w.sink.put(c->h_rows[0], at, m, res)) return e;
-    d += m;
-  }
+  if (int e = rows_to_sink(w, o, r3.count, r, res)) return e;
   o.cres.kernel_ms += r3.kernel_ms;
   o.cres.index_ms += r3.index_ms;
-  finish_walk(res, r3.format, o.cur.total, 4, o.cres, o.t_d2h + (now_ms() - td), t0);
+  finish_record_walk(res, r3.format, 4, o, t0);
   forward_error(res, r3, r3.status);
   res->reruns = r3.reruns + 1;
   return rc;
@@ -500,7 +336,7 @@ int one_pass_rest(Walk &w, WalkResult &o, shockidx_result *res, double t0) {
 // reports it.  The FASTA piece is read back from the file (it may begin before the slot holding
 // the slab).
 int finish_go_error(Walk &w, WalkResult &o, shockidx_result *res, double t0) {
-  finish_walk(res, o.kfmt, o.cur.total, 4, o.cres, o.t_d2h, t0);
+  finish_record_walk(res, o.kfmt, 4, o, t0);
   res->term_code = o.err_dr.code;
   if (o.err_dr.code == ST_FA_INVALID)
     return fasta_error_text(res, o.err_dr.err_len, [&](char *dst, u64 k) -> int {
@@ -515,17 +351,13 @@ int finish_go_error(Walk &w, WalkResult &o, shockidx_result *res, double t0) {
 // and the pinned row staging.  The caches of the other layout go first.
 int prepare_buffers(shockidx_ctx *c, const SlabLayout &lay, shockidx_result *res) {
   hipStream_t s = c->stream;
-  if (!c->s_copy) HIPCHK(hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking), "copy stream");
-  for (int i = 0; i < 2; ++i)
-    if (!c->h_rows[i]) HIPCHK(hipHostMalloc(&c->h_rows[i], STAGE_BYTES, 0), "hipHostMalloc(rows)");
+  if (int rc = walk_prereqs(c, res)) return rc;
   const u64 SLOT = RING_FRONT + lay.S + PIPE_HALO + 64;  // (kept by the context, like its other caches, until a trim)
   if (lay.ring) {
-    if (c->d_slot[0].cap != SLOT || c->d_slot[1].cap != SLOT) {
-      // the caches of earlier (larger) builds go first: the node buffer of a one-pass build, rows
-      trim_workspace(c, 0);
-      for (auto &slot : c->d_slot)
-        if (int rc = slot.exact(SLOT, res)) return rc;
-    } else if (c->d_in) {
+    // slots of another size: the caches of earlier (larger) builds go first (the node buffer of a
+    // one-pass build, rows); slots of this size: only the node buffer goes
+    if (int rc = exact_workspace(c, {{&c->d_slot[0], SLOT}, {&c->d_slot[1], SLOT}}, res)) return rc;
+    if (c->d_in) {
       (void)hipStreamSynchronize(s);
       c->d_in.drop();
     }
@@ -582,7 +414,7 @@ int build_fd_walk(shockidx_ctx *c, int fd, u64 n, int kind, int fmt, RowSink &si
       if (ring && o.cur.next_off > base) {
         // the rest from r = next_off as a node of its own, through the same slots (the caller loops)
         *restart = o.cur.next_off;
-        finish_walk(res, o.kfmt, o.cur.total, 4, o.cres, o.t_d2h, t0);
+        finish_record_walk(res, o.kfmt, 4, o, t0);
         return 0;
       }
       if (ring) return one_pass_rest(w, o, res, t0);
@@ -598,7 +430,7 @@ int build_fd_walk(shockidx_ctx *c, int fd, u64 n, int kind, int fmt, RowSink &si
   auto byte_at = [&](u64 off, uint8_t *b) { return pread(fd, b, 1, (off_t)off) == 1; };
   if (!table_ends_at_file_end(o.kfmt, o.cur.next_off, base + n, o.cur.last_len, byte_at))
     return set_msg(res, SHOCKIDX_EINTERNAL, SLAB_END_MSG);
-  finish_walk(res, o.kfmt, o.cur.total, ring ? 4 : 3, o.cres, o.t_d2h, t0);  // the slab pipeline (4: through the two slots)
+  finish_record_walk(res, o.kfmt, ring ? 4 : 3, o, t0);  // the slab pipeline (4: through the two slots)
   res->status = SHOCKIDX_OK;
   return SHOCKIDX_OK;
 }
@@ -640,409 +472,6 @@ int build_fd_pipelined(shockidx_ctx *c, int fd, u64 n, int kind, int fmt, RowSin
   }
 }
 
-// ---- the column index's walk -------------------------------------------------------------------
-// CreateColumnIndex (column.go:53-108) slab by slab through two slots: slab k + 1 is copied on the
-// copy stream (PageCacheSource: page-cache DMA, else the pinned staging, whose preads run on this
-// thread) while slab k's kernels run, each slab's rows go to the sink as they are made, and the
-// loop's state travels in the device carry.  sidx_colwalk.hpp holds the sizing and the one retry
-// rule.  The device holds the two slots, the carry with one slab's workspace (c->d_colb) and one
-// slab's rows, all exact-size.
-namespace {
-
-struct ColWalk {
-  shockidx_ctx *c;
-  u64 n, S, halo;
-  SlabEvents &events;
-  PageCacheSource &src;
-  Err res;
-  // slab p into slot i (its first byte at COLWALK_FRONT), its arrival recorded in events.ev[i]
-  int stage(int i, const ColSlabPos &p) {
-    if (int rc = src.copy_range(c->d_slot[i] + COLWALK_FRONT - p.front, p.lo - p.front, p.lo + p.end, p.lo - p.front)) return rc;
-    if (hipError_t e = hipEventRecord(events.ev[i], c->s_copy)) return set_hip(res, e, "event");
-    return 0;
-  }
-};
-
-// the slab's m rows (device rows [0, m)) through the pinned row buffers into the sink; *next: the
-// offset the table has reached (every row starts there: column.go:90-93)
-int col_rows_to_sink(shockidx_ctx *c, u64 m, ColRowCursor &cur, u64 *next, RowSink &sink, double *t_d2h,
-                     shockidx_result *res) {
-  const double td = now_ms();
-  const u64 per = STAGE_BYTES / 16;
-  int b = 0;
-  for (u64 done = 0; done < m; b ^= 1) {
-    const u64 k = m - done < per ? m - done : per;
-    HIPCHK(hipMemcpyAsync(c->h_rows[b], c->d_rows + 2 * done, k * 16, hipMemcpyDeviceToHost, c->stream), "rows copy");
-    HIPCHK(hipStreamSynchronize(c->stream), "rows copy");
-    const u64 *r = (const u64 *)c->h_rows[b];
-    for (u64 i = 0; i < k; ++i) {
-      if (r[2 * i] != *next) return set_msg(res, SHOCKIDX_EINTERNAL, SLAB_SEAM_MSG);
-      *next += r[2 * i + 1];
-    }
-    if (int rc = sink.put(c->h_rows[b], cur.take(k), k, res)) return rc;
-    done += k;
-  }
-  *t_d2h += now_ms() - td;
-  return 0;
-}
-
-}  // namespace
-
-int column_fd_walk(shockidx_ctx *c, int fd, u64 n, u32 column, u64 S, u64 halo, RowSink &sink, shockidx_result *res) {
-  const double t0 = now_ms();
-  res->path = 5;
-  res->format = SHOCKIDX_FMT_LINE;
-  if (!n) return SHOCKIDX_OK;  // one empty piece, blank: no rows (column.go:64-68,119)
-  const u64 budget = dev_budget(c);
-  const u64 carry_b = (sizeof(ColCarry) + 255) & ~255ull;
-  if (!halo) halo = colwalk_default_halo(budget);
-  if (halo > n) halo = n;
-  if (!S) {
-    S = colwalk_slab_bytes(budget, halo, carry_b, sidx_col_tile_bytes);
-    if (!S) return set_msg(res, SHOCKIDX_ENOMEM, "device memory: the column walk needs at least 32 MiB of its budget");
-  }
-  if (S > n) S = n;
-  hipStream_t s = c->stream;
-  if (!c->s_copy) HIPCHK(hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking), "copy stream");
-  for (int i = 0; i < 2; ++i)
-    if (!c->h_rows[i]) HIPCHK(hipHostMalloc(&c->h_rows[i], STAGE_BYTES, 0), "hipHostMalloc(rows)");
-  const u64 slot = colwalk_slot_bytes(S, halo), ws_b = sidx_col_tile_bytes((S + TILE - 1) / TILE);
-  u64 row_cap = colwalk_rows_cap(S);
-  if (c->d_slot[0].cap != slot || c->d_slot[1].cap != slot || c->d_colb.cap != carry_b + ws_b || c->d_rows.cap != row_cap) {
-    trim_workspace(c, 0);  // the caches of other builds go first
-    for (auto &sl : c->d_slot)
-      if (int rc = sl.exact(slot, res)) return rc;
-    if (int rc = c->d_colb.exact(carry_b + ws_b, res)) return rc;
-    if (int rc = c->d_rows.exact(row_cap, res)) return rc;
-  }
-  ColCarry *carry = c->d_colb.as<ColCarry>();
-  void *ws = c->d_colb + carry_b;
-  SlabEvents events(2, c->s_copy);  // (outlives the source's copies)
-  HIPCHK(events.create(), "event");
-  PageCacheSource src(c, fd, 0, n, res);
-  ColWalk w{c, n, S, halo, events, src, res};
-  ColRowCursor cur;
-  u64 next = 0;
-  double t_d2h = 0;
-  int i = 0;
-  ColSlabPos p = colwalk_slab_at(0, S, halo, n);
-  int rc = w.stage(0, p);
-  while (!rc) {
-    bool more = !p.last;
-    ColSlabPos q = p;
-    if (more) {  // the slab expected next, on its way while this one is indexed
-      q = colwalk_slab_at(p.lo + p.n, S, halo, n);
-      if ((rc = w.stage(i ^ 1, q))) break;
-    }
-    if (hipError_t e = hipStreamWaitEvent(s, events.ev[i], 0)) { rc = set_hip(res, e, "wait slab"); break; }
-    shockidx_result r2;
-    bool moved = false;
-    for (;;) {
-      reset_result(&r2);
-      const ColSlabIn in{c->d_slot[i] + COLWALK_FRONT, p.n, p.end, p.front, p.lo, n, p.first, p.last};
-      rc = column_slab_run(c, in, column, ws, carry, c->d_rows, row_cap, s, &r2);
-      res->kernel_ms += r2.kernel_ms;
-      if (rc == SHOCKIDX_ESPACE) {  // more cuts than a row per 32 bytes: the rows grow
-        row_cap = colwalk_grow_rows(row_cap, r2.count);
-        res->reruns++;
-        if ((rc = c->d_rows.exact(row_cap, res))) break;
-        continue;
-      }
-      if (rc == SHOCKIDX_EMORE) {  // the retry rule (sidx_colwalk.hpp)
-        u64 cut = 0;
-        if (colwalk_on_more(p.lo, r2.state_out, &cut) == ColRetry::NoMem) {
-          rc = set_msg(res, SHOCKIDX_ENOMEM, "device memory: a line or its key is longer than a slab slot can hold");
-          break;
-        }
-        p = colwalk_shorten(p, cut - p.lo, halo, n);
-        q = colwalk_slab_at(cut, S, halo, n);
-        more = moved = true;
-        res->reruns++;
-        continue;
-      }
-      if (rc) forward_error(res, r2, rc);
-      break;
-    }
-    if (rc) break;
-    if ((rc = col_rows_to_sink(c, r2.count, cur, &next, sink, &t_d2h, res))) break;
-    if (!more) break;
-    if (moved && (rc = w.stage(i ^ 1, q))) break;  // a fresh slot from where the shortened slab ends
-    p = q;
-    i ^= 1;
-  }
-  const hipError_t se = src.drain();  // before the pages are unpinned and unmapped
-  if (se != hipSuccess && rc >= 0 && rc != SHOCKIDX_EFORMAT) rc = set_hip(res, se, "H2D sync");
-  if (rc) {
-    res->count = 0;  // (column.go:76 returns count 0; an error leaves no table)
-    return rc;
-  }
-  if (cur.total && next != n) return set_msg(res, SHOCKIDX_EINTERNAL, SLAB_END_MSG);
-  res->count = cur.total;
-  res->index_ms = res->kernel_ms;
-  res->d2h_ms = t_d2h;
-  res->total_ms = now_ms() - t0;
-  res->h2d_ms = res->total_ms - t_d2h - res->kernel_ms;
-  res->status = SHOCKIDX_OK;
-  return SHOCKIDX_OK;
-}
-
-// ---- the subset indexes' walk ------------------------------------------------------------------
-// CreateSubsetNodeIndexes / CreateSubsetIndex (subset.go:186-291) over the two files: the id text
-// slab by slab through the two slots (slab k + 1 copied on the copy stream while slab k runs), the
-// parent index window by window (pread, as the reference's ReadAt per id: the first window from row
-// 0, after a stop at an id the next from that id's row), each call's rows and runs to the sinks as
-// they are made, the loop's state in the device carry.  sidx_subwalk.hpp holds the sizing and the
-// decisions.  The device holds the two slots, the window, the carry with one slab's runs, one
-// call's workspace (c->d_sends, c->d_sub) and one slab's rows, all sized up front.
-namespace {
-
-// m rows of a device table through a pinned buffer into a sink, numbered from `first`
-int sub_table_to_sink(shockidx_ctx *c, const u64 *d_tab, u64 m, u64 first, RowSink &sink, Err res) {
-  const u64 per = STAGE_BYTES / 16;
-  for (u64 done = 0; done < m;) {
-    const u64 k = m - done < per ? m - done : per;
-    HIPCHK(hipMemcpyAsync(c->h_rows[0], d_tab + 2 * done, k * 16, hipMemcpyDeviceToHost, c->stream), "rows copy");
-    HIPCHK(hipStreamSynchronize(c->stream), "rows copy");
-    if (int rc = sink.put(c->h_rows[0], first + done, k, res)) return rc;
-    done += k;
-  }
-  return 0;
-}
-
-// rows [w.row0, w.row0 + w.rows) of the parent index file into the window buffer
-int sub_load_window(shockidx_ctx *c, int fd, const SubWindow &w, Err res) {
-  const u64 per = STAGE_BYTES;
-  for (u64 done = 0, total = 16 * w.rows; done < total;) {
-    const u64 k = total - done < per ? total - done : per;
-    for (u64 got = 0; got < k;) {
-      const ssize_t r = pread(fd, c->h_rows[1] + got, k - got, (off_t)(16 * w.row0 + done + got));
-      if (r < 0 && errno == EINTR) continue;
-      if (r < 0) return set_msg(res, SHOCKIDX_EIO, std::string("read: ") + strerror(errno));
-      if (r == 0) return set_msg(res, SHOCKIDX_EIO, "read: the parent index file is shorter than its size");
-      got += (u64)r;
-    }
-    HIPCHK(hipMemcpyAsync(c->d_spar + done, c->h_rows[1], k, hipMemcpyHostToDevice, c->stream), "window copy");
-    HIPCHK(hipStreamSynchronize(c->stream), "window copy");
-    done += k;
-  }
-  return 0;
-}
-
-}  // namespace
-
-int subset_fd_walk(shockidx_ctx *c, int ids_fd, u64 n, int parent_fd, u64 parent_bytes, i64 ilength, bool want_runs,
-                   u64 S, u64 W, SubsetSinks sinks, shockidx_subset_result *res) {
-  const double t0 = now_ms();
-  shockidx_subset_stats &st = c->subset_stats;
-  memset(&st, 0, sizeof st);
-  st.walked = 1;
-  if (!n) return SHOCKIDX_OK;  // no line: two empty tables (:186-195,274-291)
-  const u64 parent_count = parent_bytes / 16, budget = dev_budget(c);
-  const u64 carry_b = (sizeof(SubCarry) + 255) & ~255ull;
-  u64 halo = SUBWALK_HALO < n ? SUBWALK_HALO : n;
-  if (!W) W = subwalk_window_rows(budget, parent_count);
-  if (W > parent_count) W = parent_count ? parent_count : 1;
-  if (!S) {
-    S = subwalk_slab_bytes(budget, halo, W, carry_b, subset_slab_ws_bytes);
-    if (!S) return set_msg(res, SHOCKIDX_ENOMEM, "device memory: the subset walk needs at least 32 MiB of its budget");
-  }
-  if (S > n) S = n;
-  st.slab_bytes = S;
-  st.window_rows = W;
-  hipStream_t s = c->stream;
-  if (!c->s_copy) HIPCHK(hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking), "copy stream");
-  for (int i = 0; i < 2; ++i)
-    if (!c->h_rows[i]) HIPCHK(hipHostMalloc(&c->h_rows[i], STAGE_BYTES, 0), "hipHostMalloc(rows)");
-  const u64 slot = subwalk_slot_bytes(S, halo), rows_cap = subwalk_rows_cap(S), runs_cap = subwalk_runs_cap(S);
-  u64 ends_b = 0, line_b = 0;  // a call's workspace, sized for the longest window so that no call grows it
-  subset_slab_ws_parts(S + halo, &ends_b, &line_b);
-  if (c->d_slot[0].cap != slot || c->d_slot[1].cap != slot || c->d_spar.cap != 16 * W || c->d_rows.cap != rows_cap ||
-      c->d_sruns.cap != carry_b + 16 * runs_cap || c->d_sends.cap != ends_b || c->d_sub.cap != line_b) {
-    trim_workspace(c, 0);  // the caches of other builds go first
-    for (auto &sl : c->d_slot)
-      if (int rc = sl.exact(slot, res)) return rc;
-    if (int rc = c->d_spar.exact(16 * W, res)) return rc;
-    if (int rc = c->d_rows.exact(rows_cap, res)) return rc;
-    if (int rc = c->d_sruns.exact(carry_b + 16 * runs_cap, res)) return rc;
-    if (int rc = c->d_sends.exact(ends_b, res)) return rc;
-    if (int rc = c->d_sub.exact(line_b, res)) return rc;
-  }
-  SubCarry *carry = c->d_sruns.as<SubCarry>();
-  u64 *d_runs = (u64 *)(c->d_sruns + carry_b);
-  HIPCHK(hipMemsetAsync(carry, 0, carry_b, s), "carry");
-  SlabEvents events(2, c->s_copy);  // (outlives the source's copies)
-  HIPCHK(events.create(), "event");
-  PageCacheSource src(c, ids_fd, 0, n, res);
-  ColWalk w{c, n, S, halo, events, src, res};
-  SubCursor cur;
-  SubWindow win = subwalk_window_at(0, W, parent_count);
-  int rc = sub_load_window(c, parent_fd, win, res);
-  st.windows = 1;
-  st.parent_bytes = 16 * win.rows;
-  int i = 0;
-  ColSlabPos p = colwalk_slab_at(0, S, halo, n);
-  if (!rc) rc = w.stage(0, p);
-  st.ids_bytes = p.end;
-  shockidx_subset_slab_result r2;
-  memset(&r2, 0, sizeof r2);
-  while (!rc) {
-    bool more = !p.last, moved = false;
-    ColSlabPos q = p;
-    if (more) {  // the slab expected next, on its way while this one runs
-      q = colwalk_slab_at(p.lo + p.n, S, halo, n);
-      if ((rc = w.stage(i ^ 1, q))) break;
-      st.ids_bytes += q.end + q.front;
-    }
-    if (hipError_t e = hipStreamWaitEvent(s, events.ev[i], 0)) { rc = set_hip(res, e, "wait slab"); break; }
-    st.slabs++;
-    for (;;) {
-      shockidx_slab sl;
-      memset(&sl, 0, sizeof sl);
-      sl.d_data = c->d_slot[i] + COLWALK_FRONT;
-      sl.n = p.n; sl.end = p.end; sl.front = p.front; sl.base = p.lo;
-      sl.is_first = p.first; sl.is_last = p.last;
-      rc = shockidx_subset_slab_device(c, &sl, n, c->d_spar, win.row0, win.rows, parent_count, ilength, want_runs, carry,
-                                       c->d_rows, rows_cap, d_runs, runs_cap, &r2);
-      st.calls++;
-      res->kernel_ms += r2.kernel_ms;
-      if (rc != SHOCKIDX_OK && rc != SHOCKIDX_EFORMAT) {
-        if (rc == SHOCKIDX_ESPACE) rc = set_msg(res, SHOCKIDX_EINTERNAL, "internal error: a slab's tables are short");
-        else forward_error(res, r2, rc);
-        break;
-      }
-      const int rc_call = rc;
-      if ((rc = sub_table_to_sink(c, c->d_rows, r2.rows, cur.take_rows(r2.rows), *sinks.rows, res))) break;
-      if (want_runs && (rc = sub_table_to_sink(c, d_runs, r2.runs, cur.take_runs(r2.runs), *sinks.runs, res))) break;
-      if (rc_call == SHOCKIDX_EFORMAT) { rc = forward_error(res, r2, SHOCKIDX_EFORMAT); break; }
-      if (r2.stop == 2) {  // the same slab against the window that starts at the id's row
-        win = subwalk_next_window(r2.next_id, W, parent_count);
-        if ((rc = sub_load_window(c, parent_fd, win, res))) break;
-        st.windows++;
-        st.parent_bytes += 16 * win.rows;
-        continue;
-      }
-      if (r2.stop == 1) {
-        if (subwalk_on_open_line(p.lo, r2.next_off) == SubRetry::NoMem) {
-          rc = set_msg(res, SHOCKIDX_ENOMEM, "device memory: an id line is longer than a slab slot can hold");
-          break;
-        }
-        q = colwalk_slab_at(r2.next_off, S, halo, n);
-        more = moved = true;
-      }
-      break;
-    }
-    if (rc || !more) break;
-    if (moved) {  // a fresh slot from the open line on
-      if ((rc = w.stage(i ^ 1, q))) break;
-      st.ids_bytes += q.end + q.front;
-    }
-    p = q;
-    i ^= 1;
-  }
-  const hipError_t se = src.drain();  // before the pages are unpinned and unmapped
-  if (se != hipSuccess && rc >= 0 && rc != SHOCKIDX_EFORMAT) rc = set_hip(res, se, "H2D sync");
-  st.held_bytes = workspace_bytes(c);
-  if (rc == SHOCKIDX_OK || rc == SHOCKIDX_EFORMAT) {
-    res->count = r2.count;
-    res->runs = r2.nruns;
-    res->size = r2.size;
-  }
-  res->total_ms = now_ms() - t0;
-  return rc;
-}
-
-// ---- the chunkrecord index's walk --------------------------------------------------------------
-// chunkRecord.Create (chunkrecord.go:41-99) slab by slab through two slots: slot k holds file bytes
-// [max(0, k S - H), min(n, (k + 1) S)) from its first byte on, slab k + 1 is copied on the copy
-// stream while slab k is walked, each slab's rows go to the sink as they are made, and the loop's
-// state travels in the device carry.  sidx_chunkwalk.hpp holds the layout, the sizing and the reason
-// no slab is ever submitted twice.  The device holds the two slots, the carry, one slab's
-// workspace (c->d_cra, c->d_crb and, for FASTQ, the tile block of the view's record index) and one
-// slab's rows.
-int chunk_fd_walk(shockidx_ctx *c, int fd, u64 n, int fmt, u64 chunk, u64 S, RowSink &sink, shockidx_result *res) {
-  const double t0 = now_ms();
-  res->path = 6;
-  hipStream_t s = c->stream;
-  if (!S) {
-    const u64 top = n < CHUNKWALK_MAX_SLAB ? n : CHUNKWALK_MAX_SLAB;
-    S = chunkwalk_slab_bytes(dev_budget(c), chunk, chunk_walk_dev(c, top + CHUNKWALK_HALO));
-    if (!S) return set_msg(res, SHOCKIDX_ENOMEM, "device memory: the chunkrecord walk needs at least 32 MiB of its budget");
-  }
-  if (S > n) S = n ? n : 1;
-  const u64 vmax = S + CHUNKWALK_HALO;
-  const ChunkWalkDev dv = chunk_walk_dev(c, vmax);
-  if (!c->s_copy) HIPCHK(hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking), "copy stream");
-  for (int i = 0; i < 2; ++i)
-    if (!c->h_rows[i]) HIPCHK(hipHostMalloc(&c->h_rows[i], STAGE_BYTES, 0), "hipHostMalloc(rows)");
-  const u64 slot = chunkwalk_slot_bytes(S), cra = chunkwalk_cra_bytes(vmax, dv.scan_bytes, dv.gslot),
-            crb = chunkwalk_crb_bytes(vmax, chunk), row_cap = chunkwalk_row_bound(vmax, chunk);
-  if (c->d_slot[0].cap != slot || c->d_slot[1].cap != slot || c->d_cra.cap != cra || c->d_crb.cap != crb ||
-      c->d_crc.cap != dv.carry_bytes || c->d_rows.cap != row_cap) {
-    trim_workspace(c, 0);  // the caches of other builds go first
-    for (auto &sl : c->d_slot)
-      if (int rc = sl.exact(slot, res)) return rc;
-    if (int rc = c->d_cra.exact(cra, res)) return rc;
-    if (int rc = c->d_crb.exact(crb, res)) return rc;
-    if (int rc = c->d_crc.exact(dv.carry_bytes, res)) return rc;
-    if (int rc = c->d_rows.exact(row_cap, res)) return rc;
-  }
-  ChunkCarry *carry = c->d_crc.as<ChunkCarry>();
-  SlabEvents events(2, c->s_copy);  // (outlives the source's copies)
-  HIPCHK(events.create(), "event");
-  PageCacheSource src(c, fd, 0, n, res);
-  auto stage = [&](u64 k) -> int {  // slab k into slot k mod 2, its arrival recorded in that slot's event
-    const ChunkSlot p = chunkwalk_slot(k, S, n);
-    if (p.hi > p.lo)
-      if (int rc = src.copy_range(c->d_slot[k & 1], p.lo, p.hi, p.lo)) return rc;
-    if (hipError_t e = hipEventRecord(events.ev[k & 1], c->s_copy)) return set_hip(res, e, "event");
-    return 0;
-  };
-  const u64 K = chunkwalk_slots(S, n);
-  ColRowCursor cur;
-  u64 next = 0;
-  double t_d2h = 0;
-  int kfmt = 0;
-  int rc = stage(0);
-  for (u64 k = 0; !rc && k < K; ++k) {
-    if (k + 1 < K && (rc = stage(k + 1))) break;  // the next slab, on its way while this one is walked
-    if (hipError_t e = hipStreamWaitEvent(s, events.ev[k & 1], 0)) { rc = set_hip(res, e, "wait slab"); break; }
-    const ChunkSlot p = chunkwalk_slot(k, S, n);
-    const ChunkView v{c->d_slot[k & 1], p.lo, p.hi, n, p.last};
-    if (k == 0) {  // the first slab resolves the format (S >= 64 KiB: it holds the bytes detection reads)
-      if ((rc = resolve_format(c, v.d, v.hi, SHOCKIDX_RECORD, fmt, s, &kfmt, res))) break;
-      res->format = kfmt;
-      if (kfmt == SHOCKIDX_FMT_SAM) {
-        rc = set_msg(res, SHOCKIDX_EFORMAT, "chunkrecord: sam.SeekChunk never advances (reference loops forever)");
-        break;
-      }
-      if (kfmt != SHOCKIDX_FMT_FASTA && kfmt != SHOCKIDX_FMT_FASTQ) { rc = set_msg(res, SHOCKIDX_EINVAL, "invalid format"); break; }
-    }
-    shockidx_result r2;
-    reset_result(&r2);
-    rc = chunk_slab_run(c, v, chunk, k == 0, kfmt, carry, c->d_rows, row_cap, s, &r2);
-    res->kernel_ms += r2.kernel_ms;
-    res->reruns += r2.reruns;
-    if (rc == SHOCKIDX_ESPACE) rc = set_msg(res, SHOCKIDX_EINTERNAL, "internal error: a slab's rows exceed their bound");
-    else if (rc) forward_error(res, r2, rc);
-    if (rc) break;
-    rc = col_rows_to_sink(c, r2.count, cur, &next, sink, &t_d2h, res);
-  }
-  const hipError_t se = src.drain();  // before the pages are unpinned and unmapped
-  if (se != hipSuccess && rc >= 0 && rc != SHOCKIDX_EFORMAT) rc = set_hip(res, se, "H2D sync");
-  if (rc) {
-    res->count = 0;
-    return rc;
-  }
-  if (next != n) return set_msg(res, SHOCKIDX_EINTERNAL, SLAB_END_MSG);
-  res->count = cur.total;
-  res->index_ms = res->kernel_ms;
-  res->d2h_ms = t_d2h;
-  res->total_ms = now_ms() - t0;
-  res->h2d_ms = res->total_ms - t_d2h - res->kernel_ms;
-  res->status = SHOCKIDX_OK;
-  return SHOCKIDX_OK;
-}
-
 // Slab-pipelined FASTQ record build of a pinned host body: the body crosses PCIe in 1 GiB
 // slabs on a copy stream while the compute stream indexes slab k as soon as its bytes and a
 // 4 MiB halo have arrived, with slab k - 1's exact end state as its incoming state (the slab
@@ -1059,7 +488,7 @@ int build_host_pipelined(shockidx_ctx *c, const void *data, u64 n, int kind, int
     return 0;
   const double t0 = now_ms();
   hipStream_t s = c->stream;
-  if (!c->s_copy) HIPCHK(hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking), "copy stream");
+  if (int rc = walk_prereqs(c, res, false)) return rc;  // (its rows go straight to the table: no row buffers)
   if (int rc = c->d_in.ensure(n + 64, res)) return rc;
   const SlabLayout lay{n, PIPE_SLAB, false};
   const u64 K = lay.count();

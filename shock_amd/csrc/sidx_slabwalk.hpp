@@ -39,6 +39,21 @@ inline u64 ring_slab_bytes(u64 budget) {
   return S < RING_MIN_SLAB ? 0 : S;
 }
 
+// The sizing of the carried-state walks (sidx_colwalk.hpp, sidx_subwalk.hpp, sidx_chunkwalk.hpp):
+// the largest multiple of `align`, at most `max`, whose footprint fits(S) the budget; 0: none
+// does.  A footprint grows with S, so fits holds up to some S and fails above it: a bisection on
+// S / align.
+template <class Fits>
+u64 largest_slab(u64 align, u64 max, Fits fits) {
+  u64 lo = 0, hi = max / align;
+  while (lo < hi) {
+    const u64 mid = (lo + hi + 1) / 2;
+    if (fits(mid * align)) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo * align;
+}
+
 // What a slab's index pass (run_index's code rc, its device result) means for the walk.
 enum class SlabOutcome {
   Clean,     // its rows continue the table, on to the next slab

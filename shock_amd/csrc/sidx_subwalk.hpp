@@ -1,5 +1,5 @@
 // sidx_subwalk.hpp -- the arithmetic and decisions of the subset indexes' slab walk
-// (shockidx_subset_fd_walk, sidx_pipeline.cpp) that need no device: how large an id slab and a
+// (shockidx_subset_fd_walk, sidx_walks.cpp) that need no device: how large an id slab and a
 // parent window a device budget allows, which window follows a stop at an id, what a line that
 // does not close means for the walk, and the row and run cursors.  No HIP calls, so
 // tests/host/subwalk_test.cpp exercises every piece on the CPU.
@@ -44,13 +44,7 @@ u64 subwalk_footprint(u64 S, u64 halo, u64 W, u64 carry_bytes, WsBytes ws) {
 template <class WsBytes>
 u64 subwalk_slab_bytes(u64 budget, u64 halo, u64 W, u64 carry_bytes, WsBytes ws) {
   if (budget < SUBWALK_MIN_BUDGET) return 0;
-  u64 lo = 0, hi = SUBWALK_MAX_SLAB / SUBWALK_ALIGN;  // (the footprint grows with S: bisect on S / ALIGN)
-  while (lo < hi) {
-    const u64 mid = (lo + hi + 1) / 2;
-    if (subwalk_footprint(mid * SUBWALK_ALIGN, halo, W, carry_bytes, ws) <= budget) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo * SUBWALK_ALIGN;
+  return largest_slab(SUBWALK_ALIGN, SUBWALK_MAX_SLAB, [&](u64 S) { return subwalk_footprint(S, halo, W, carry_bytes, ws) <= budget; });
 }
 
 // The window after a call stopped at id next_id (stop 2): it starts at that id's row, so a sparse

@@ -1,6 +1,6 @@
 // colwalk_test.cpp -- CPU test of the column slab walk's arithmetic in
 // shock_amd/csrc/sidx_colwalk.hpp: the slab a device budget allows (at and just under the smallest
-// budget, never over the budget), where a slab lies in its slot, the one retry rule (shorten /
+// budget, never over the budget; the shared bisect on its own), where a slab lies in its slot, the one retry rule (shorten /
 // advance / no slot can hold the line) and the row cursor.
 // Stand-alone: it includes that header only, links nothing of the library and makes no HIP call.
 // Built with the host sanitizers by `make -C shock_amd/csrc colwalk_test`; exit 0 = every check held.
@@ -47,6 +47,30 @@ static void test_sizing() {
   CHECK(colwalk_slab_bytes(1ull << 40, COLWALK_HALO, CARRY, ws_model) == (1ull << 30));
   CHECK(colwalk_rows_cap(0) == 4096 && colwalk_rows_cap(1ull << 20) == 32768 + 4096);
   CHECK(colwalk_slot_bytes(TILE, 4096) == COLWALK_FRONT + TILE + 4096 + COLWALK_PAD);
+}
+
+// the bisect the three walks' sizing shares (largest_slab, sidx_slabwalk.hpp)
+static void test_largest_slab() {
+  u64 calls = 0;
+  CHECK(largest_slab(4096, 1ull << 30, [&](u64) { ++calls; return false; }) == 0 && calls > 0);  // fits nothing
+  CHECK(largest_slab(4096, 1ull << 30, [](u64) { return true; }) == (1ull << 30));               // fits everything
+  CHECK(largest_slab(1000, 4500, [](u64) { return true; }) == 4000);  // a max off a multiple: the multiple below it
+  // a threshold S <= T: the largest multiple of align that is <= min(T, max), T on and off a multiple
+  const u64 aligns[] = {1, 4096, 1ull << 20}, maxes[] = {1ull << 20, 256ull << 20, 1ull << 30};
+  for (u64 align : aligns)
+    for (u64 max : maxes) {
+      const u64 qs[] = {0, 1, 2, 77, max / align - 1, max / align, max / align + 1, 4 * (max / align)};
+      const u64 offs[] = {0, 1, align / 2, align - 1};
+      for (u64 q : qs)
+        for (u64 off : offs) {
+          if (off >= align) continue;  // (align 1 has only T on a multiple)
+          const u64 T = q * align + off, top = T < max ? T : max;
+          u64 asked_over = 0;
+          const u64 S = largest_slab(align, max, [&](u64 s) { asked_over += s > max || s % align != 0 || s == 0; return s <= T; });
+          CHECK(S == top / align * align);
+          CHECK(asked_over == 0);  // the predicate only ever sees positive multiples within max
+        }
+    }
 }
 
 static void test_slabs() {
@@ -107,6 +131,7 @@ static void test_cursor() {
 
 int main() {
   test_sizing();
+  test_largest_slab();
   test_slabs();
   test_retry();
   test_cursor();

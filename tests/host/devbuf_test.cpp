@@ -1,5 +1,5 @@
 // devbuf_test.cpp -- CPU test of the host bookkeeping in shock_amd/csrc/sidx_devbuf.hpp: the
-// device-buffer set (growth, exact-size slots, the tile block, trims, the final free) over a fake
+// device-buffer set (growth, exact-size slots and sets, the tile block, trims, the final free) over a fake
 // allocator, and the error sink over both result structs.  Stand-alone: it includes that header
 // only, links nothing of the library and makes no HIP call.  The fake allocator is malloc / free,
 // so a double free or a leak is a sanitizer report.  Built with the host sanitizers by
@@ -162,6 +162,68 @@ static void test_slots() {
   CHECK(c.bufs.bytes() == 100 && c.trim(0) && c.bufs.bytes() == 0);
 }
 
+// the exact-size workspace of a slab walk (BufSet::exact)
+static void test_exact_set() {
+  Caches c;
+  shockidx_result r;
+  memset(&r, 0, sizeof r);
+  auto quiesce = [&] { ++c.quiesced; };
+  // from nothing: each buffer allocated in list order (the slots first), nothing to drop
+  const int a0 = n_alloc, f0 = n_free;
+  CHECK(c.bufs.exact({{&c.slot[0], 5000}, {&c.slot[1], 5000}, {&c.rows, 100}}, quiesce, &r) == 0);
+  CHECK(n_alloc == a0 + 3 && n_free == f0 && c.quiesced == 0 && last_bytes == 100 * 16);  // (the rows came last)
+  CHECK(c.slot[0].cap == 5000 && c.slot[1].cap == 5000 && c.rows.cap == 100 && c.bufs.bytes() == 2 * 5000 + 1600);
+  // every size matches: no free, no allocation, no quiesce -- the caches of other builds stay too
+  CHECK(c.in.ensure(10, &r) == 0 && c.tiles(8, &r) == 0);
+  const int a1 = n_alloc, f1 = n_free;
+  const void *p0 = c.slot[0].get(), *pr = c.rows.get(), *pin = c.in.get();
+  CHECK(c.bufs.exact({{&c.slot[0], 5000}, {&c.slot[1], 5000}, {&c.rows, 100}}, quiesce, &r) == 0);
+  CHECK(n_alloc == a1 && n_free == f1 && c.quiesced == 0);
+  CHECK(c.slot[0].get() == p0 && c.rows.get() == pr && c.in.get() == pin && c.status);
+  // one size differs: everything is dropped first (the other caches and the tile block with it),
+  // then each listed buffer is allocated, in list order, to exactly its size
+  static size_t order[4];
+  static int n_order;
+  n_order = 0;
+  const DevAlloc logging = {[](void **p, size_t bytes, bool node) {
+                              if (n_order < 4) order[n_order++] = bytes;
+                              return fake_alloc(p, bytes, node);
+                            },
+                            fake_release, fake_errstr};
+  {
+    BufSet set(&logging);
+    DevBuf<uint8_t> a{set}, b{set}, other{set};
+    DevBuf<u64> tile{set, BufClass::Tile};
+    DevBuf<u64, 2> rows{set};
+    int q = 0;
+    CHECK(set.exact({{&a, 300}, {&b, 300}, {&rows, 7}}, [&] { ++q; }, &r) == 0 && q == 0);
+    CHECK(other.ensure(50, &r) == 0 && tile.exact(9, &r) == 0);
+    n_order = 0;
+    const int a2 = n_alloc, f2 = n_free;
+    bool quiesced_first = false;  // (before anything is freed)
+    auto before_drop = [&] { ++q; quiesced_first = n_alloc == a2 && n_free == f2; };
+    CHECK(set.exact({{&a, 300}, {&b, 300}, {&rows, 8}}, before_drop, &r) == 0);
+    CHECK(quiesced_first && q == 1 && n_free == f2 + 5 && n_alloc == a2 + 3);  // all five went, three came back
+    CHECK(n_order == 3 && order[0] == 300 && order[1] == 300 && order[2] == 8 * 16);
+    CHECK(a.cap == 300 && b.cap == 300 && rows.cap == 8 && !other && !tile && set.bytes() == 600 + 128);
+    // an allocation fails midway: its error, the buffers before it held, it and the rest empty,
+    // the count right -- and the next call starts over
+    static int countdown;
+    countdown = 2;
+    const DevAlloc failing = {[](void **p, size_t bytes, bool node) { return --countdown == 0 ? 2 : fake_alloc(p, bytes, node); },
+                              fake_release, fake_errstr};
+    BufSet set2(&failing);
+    DevBuf<uint8_t> s0{set2, BufClass::Large, true, "hipMalloc(slab slot)"}, s1{set2, BufClass::Large, true, "hipMalloc(slab slot)"};
+    DevBuf<u64, 2> rows2{set2};
+    CHECK(set2.exact({{&s0, 64}, {&s1, 64}, {&rows2, 4}}, [] {}, &r) == SHOCKIDX_EHIP);
+    CHECK(r.status == SHOCKIDX_EHIP && !strcmp(r.err, "hipMalloc(slab slot): out of memory"));
+    CHECK(s0 && s0.cap == 64 && !s1 && s1.cap == 0 && !rows2 && rows2.cap == 0 && set2.bytes() == 64);
+    countdown = 100;
+    CHECK(set2.exact({{&s0, 64}, {&s1, 64}, {&rows2, 4}}, [] {}, &r) == 0);
+    CHECK(s0.cap == 64 && s1.cap == 64 && rows2.cap == 4 && set2.bytes() == 128 + 64);
+  }
+}
+
 static void test_destroy() {
   const int a0 = n_alloc, f0 = n_free;
   {
@@ -223,6 +285,7 @@ int main() {
   test_failed_alloc<shockidx_subset_result>();
   test_trim();
   test_slots();
+  test_exact_set();
   test_destroy();
   test_sink<shockidx_result>();
   test_sink<shockidx_subset_result>();

@@ -77,6 +77,25 @@ def test_fd_walk_small_and_degenerate(gpu_ctx, tmp_path):
     assert e.value.code == L.ENOMEM and "slot" in e.value.msg
 
 
+def test_fd_walk_rows_past_one_pinned_chunk(gpu_ctx, tmp_path):
+    """one slab with more rows than the pinned row buffer holds (64 MiB / 16 = 4 Mi rows): the row
+    drain loops, numbers its second chunk from where the first ended and checks the table across
+    the seam.  Two-byte lines with alternating keys: every line is a row (2 i, 2)."""
+    from shock_amd import _lib as L
+    lines = (4 << 20) + 1000
+    data = b"a\nb\n" * (lines // 2)
+    assert len(data) == 8390608
+    p = _file(tmp_path, data)
+    with open(p, "rb") as f:
+        r = gpu_ctx.column_fd_walk(f.fileno(), len(data), 1, 16 << 20, 4096)  # (S is clipped to the file: one slab)
+    # the rows outgrow the slab's first table (S / 32 + 4096) once
+    assert r.status == L.OK and r.path == 5 and r.reruns == 1 and r.count == lines == 4195304
+    want = np.array(colref.expected(data, 1)[1], dtype=np.uint64).reshape(-1, 2)
+    closed = np.stack([2 * np.arange(lines, dtype=np.uint64), np.full(lines, 2, np.uint64)], axis=1)
+    assert np.array_equal(want, closed)
+    assert np.array_equal(r.rows, want)
+
+
 def test_column_create_protocol(gpu_ctx, tmp_path):
     """a node that fits the budget takes the whole-node build (path 1); the .idx is colref's table"""
     from shock_amd import _lib as L

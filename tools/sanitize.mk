@@ -14,7 +14,7 @@ ORC := oracle/shockidx_oracle.c oracle/subset_oracle.c oracle/chunk_oracle.c ora
 
 all: shock_amd/variants/libshockidx_san.so oracle/build/liboracle_san.so
 
-HOST := sidx_build sidx_pipeline sidx_capi sidx_chunk_api sidx_column_api sidx_subset_api sidx_filter_api sidx_stream_api sidx_plan_api sidx_batch_api sidx_multi
+HOST := sidx_build sidx_pipeline sidx_walks sidx_capi sidx_chunk_api sidx_column_api sidx_subset_api sidx_filter_api sidx_stream_api sidx_plan_api sidx_batch_api sidx_multi
 KERNELS := sidx_kernels sidx_control sidx_subset sidx_chunk sidx_filter sidx_column sidx_stream sidx_plan sidx_batch
 
 $(C)/build/san/%.o: $(C)/%.cpp $(wildcard $(C)/*.hpp) include/shockidx.h
