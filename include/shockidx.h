@@ -58,7 +58,8 @@ extern "C" {
  *    shockidx_column_slab_device, shockidx_column_fd_walk, shockidx_column_create (and the code
  *    SHOCKIDX_EMORE, which only shockidx_column_slab_device returns), shockidx_subset_carry_bytes,
  *    shockidx_subset_slab_device, shockidx_subset_fd_walk, shockidx_subset_create,
- *    shockidx_subset_last_stats */
+ *    shockidx_subset_last_stats, shockidx_filter_carry_bytes, shockidx_filter_slab_device,
+ *    shockidx_filter_fd_walk, shockidx_filter_fd, shockidx_filter_last_stats */
 #define SHOCKIDX_ABI_VERSION 5
 
 /* index kinds = the registry keys served (index/index.go:21-28) */
@@ -522,6 +523,80 @@ typedef struct shockidx_stream_stats {
   uint64_t by_format[3]; /* batches of FASTQ, FASTA, SAM sections */
 } shockidx_stream_stats;
 int shockidx_stream_last_stats(const shockidx_ctx *ctx, shockidx_stream_stats *out);
+
+/* ---- The download filters in slabs: a section of a node file through two device slots ------
+ * GET /node/{id}?download&filter=F streams the whole file through one filter reader
+ * (controller/node/single.go:490-526, Streamer{R: []SectionReader{nf}}), its seek / length form one
+ * section of it (single.go:194-257).  These entry points do that for a FASTQ section of any size
+ * with a bounded device footprint: fq2fa always, anonymize when the section detects as FASTQ.
+ * Offsets are section offsets: section byte 0 is the reader's offset 0, the section's end its EOF.
+ *
+ * shockidx_filter_slab_device: one slab.  The window is the section bytes [base - front, base + end);
+ * d_data is the 16-byte-aligned device address of section byte base; base may be any offset and
+ * front may be 0 (no byte before the carried position is needed).  n <= end is the bytes owned: a
+ * Read (fastq.go:50-132) that starts before base + n belongs to this slab, one that starts at or
+ * after it to the next.  is_last != 0 exactly when base + end == sec_size (with n == end that slab
+ * owns the Read at the section's very end too and ends the stream; with n < end it leaves the Reads
+ * from base + n on to a further is_last slab); seq is ignored; no byte outside the window is read.
+ * d_carry:
+ * shockidx_filter_carry_bytes() bytes of device memory, 8-byte aligned, holding in two halves (a slab
+ * reads one and writes the other) the position of the next Read, the records and bytes delivered,
+ * the filter and an ended flag; is_first initialises it (position 0).
+ *   A record is settled by a slab that is not the last when, from its Read's start, the blank lines
+ * Read skips (fastq.go:57-68) and the four lines after them each find their '\n' before base + end;
+ * on the last slab everything is settled with the section's end as EOF (the record returned with
+ * io.EOF is dropped, the "truncated" errors fire, blank lines at EOF end the stream cleanly).  The
+ * slab delivers, in order, every owned record up to the first that is not settled or that fails.
+ *   SHOCKIDX_OK: result->count records and result->size bytes were written to d_out (both may be
+ *     0), *next_pos is the carried position; after the last slab the carry is ended.
+ *   SHOCKIDX_EFORMAT: Go's text; count / size and d_out hold what was delivered before it; the
+ *     carry is ended.  anonymize over a first slab of no format: "Invalid file type for filter".
+ *   SHOCKIDX_ESPACE: result->size is the bytes this slab needs; nothing is written.
+ *   SHOCKIDX_EINVAL: the carry is ended or was made by the other filter, the carried position lies
+ *     outside [base - front, base + n], the first slab of anonymize does not hold the section's
+ *     first min(32768, sec_size) bytes from a 16-byte-aligned address (detection reads them), or it
+ *     detects as FASTA or SAM (those sections are not walked; the text says so).
+ * Anything but SHOCKIDX_OK or SHOCKIDX_EFORMAT leaves the carry as it was.  Concatenated over the
+ * slabs of a walk, d_out is what shockidx_filter_device writes for the whole section, the final
+ * status and text are the same, and the carried counts are the whole call's.
+ *
+ * shockidx_filter_fd_walk: the section [off, off + n) of fd, always slab by slab (slab_bytes 0:
+ * sized from the device budget, which must be at least 32 MiB; halo_bytes 0: the column walk's
+ * default, less under a small budget), slab k + 1 crossing PCIe while slab k runs, each slab's
+ * output written to out_fd in order with write(2) -- out_fd may be a pipe (no lseek, no pwrite;
+ * short writes and EINTR are handled; a failed write is SHOCKIDX_EIO with the errno text).  The bytes
+ * delivered before a SHOCKIDX_EFORMAT are written before the call returns (io.Copy delivers them
+ * before the reader's error, request/streamer.go:91-96).  A record that no slot can hold is
+ * SHOCKIDX_ENOMEM after the earlier bytes were written, never a short stream returned as success.
+ * result->count / size: records / bytes delivered.
+ *
+ * shockidx_filter_fd: the whole path (the section, its output and the workspace resident at once)
+ * when that fits the device budget by a worst-case bound, else the walk.  anonymize detects from
+ * the section's first 32 KiB first: FASTQ as above; FASTA and SAM take the whole path, or
+ * SHOCKIDX_ENOMEM with a text naming the format when they do not fit; no format is SHOCKIDX_EFORMAT
+ * with nothing written. */
+uint64_t shockidx_filter_carry_bytes(void);
+int shockidx_filter_slab_device(shockidx_ctx *ctx, const char *filter, const shockidx_slab *slab,
+                                uint64_t sec_size, void *d_carry, void *d_out, uint64_t out_cap,
+                                uint64_t *next_pos, shockidx_subset_result *result);
+int shockidx_filter_fd_walk(shockidx_ctx *ctx, const char *filter, int fd, uint64_t off, uint64_t n, int out_fd,
+                            uint64_t slab_bytes, uint64_t halo_bytes, shockidx_subset_result *result);
+int shockidx_filter_fd(shockidx_ctx *ctx, const char *filter, int fd, uint64_t off, uint64_t n, int out_fd,
+                       shockidx_subset_result *result);
+
+/* How the context's last shockidx_filter_fd / shockidx_filter_fd_walk call ran. */
+typedef struct shockidx_filter_stats {
+  uint64_t path;        /* 1: the whole path, 2: the walk */
+  uint64_t slabs;       /* slab calls that ran (the walk) */
+  uint64_t restarts;    /* slabs restarted at a record its halo did not settle */
+  uint64_t slab_bytes;  /* the walk's slab and halo */
+  uint64_t halo_bytes;
+  uint64_t peak_bytes;  /* device bytes the context's caches held at the call's end (its peak) */
+  uint64_t kernel_us;   /* where the call's time went: device work, the output's way to the host, */
+  uint64_t d2h_us;      /*   write(2), */
+  uint64_t write_us;
+} shockidx_filter_stats;
+int shockidx_filter_last_stats(const shockidx_ctx *ctx, shockidx_filter_stats *out);
 
 /* ---- The download plan: all parts of an index download in one call -------------------------
  * controller/node/single.go:372-483 builds the Streamer's section list (s.R) part by part: a request

@@ -41,6 +41,8 @@ EXPORTS = ("shockidx_ctx_create", "shockidx_ctx_destroy", "shockidx_build_device
            "shockidx_subset_carry_bytes", "shockidx_subset_slab_device", "shockidx_subset_fd_walk", "shockidx_subset_create",
            "shockidx_subset_last_stats",
            "shockidx_idx_part", "shockidx_idx_range", "shockidx_filter_device", "shockidx_stream_filter_device", "shockidx_stream_last_stats",
+           "shockidx_filter_carry_bytes", "shockidx_filter_slab_device", "shockidx_filter_fd_walk", "shockidx_filter_fd",
+           "shockidx_filter_last_stats",
            "shockidx_build_batch_device", "shockidx_build_batch_host", "shockidx_batch_error", "shockidx_batch_last_stats",
            "shockidx_download_plan", "shockidx_ctx_trim",
            "shockidx_ctx_workspace_bytes", "shockidx_ctx_set_dev_cap", "shockidx_multi_create", "shockidx_multi_destroy", "shockidx_multi_rccl",
@@ -123,6 +125,22 @@ class StreamStats(ctypes.Structure):
     """mirrors shockidx_stream_stats (include/shockidx.h)"""
     _fields_ = [("sections", ctypes.c_uint64), ("batches", ctypes.c_uint64), ("batched", ctypes.c_uint64),
                 ("singles", ctypes.c_uint64), ("by_format", ctypes.c_uint64 * 3)]
+
+
+class FilterStats(ctypes.Structure):
+    """mirrors shockidx_filter_stats (include/shockidx.h)"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("path", "slabs", "restarts", "slab_bytes", "halo_bytes", "peak_bytes",
+                                               "kernel_us", "d2h_us", "write_us")]
+
+
+class FilterCarryHalf(ctypes.Structure):
+    """one half of the filter slab carry (shock_amd/csrc/sidx_common.hpp FiltCarryHalf): read by tests and tools"""
+    _fields_ = [("pos", ctypes.c_uint64), ("count", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
+                ("kind", ctypes.c_uint64), ("ended", ctypes.c_uint64), ("pad", ctypes.c_uint64 * 3)]
+
+
+class FilterCarry(ctypes.Structure):
+    _fields_ = [("cur", ctypes.c_uint64), ("pad", ctypes.c_uint64 * 7), ("half", FilterCarryHalf * 2)]
 
 
 class BatchItem(ctypes.Structure):
@@ -267,6 +285,19 @@ def lib():
     L.shockidx_stream_filter_device.argtypes = [vp, ctypes.c_char_p, vp, u64, vp, u64, vp, u64,
                                                 ctypes.POINTER(ctypes.c_int64), PSub]
     L.shockidx_stream_filter_device.restype = i32
+    if hasattr(L, "shockidx_filter_slab_device") or not os.environ.get("SHOCKIDX_VARIANT"):
+        # (a variant library of older sources has none)
+        L.shockidx_filter_carry_bytes.argtypes = []
+        L.shockidx_filter_carry_bytes.restype = u64
+        L.shockidx_filter_slab_device.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(Slab), u64, vp, vp, u64,
+                                                  ctypes.POINTER(ctypes.c_uint64), PSub]
+        L.shockidx_filter_slab_device.restype = i32
+        L.shockidx_filter_fd_walk.argtypes = [vp, ctypes.c_char_p, i32, u64, u64, i32, u64, u64, PSub]
+        L.shockidx_filter_fd_walk.restype = i32
+        L.shockidx_filter_fd.argtypes = [vp, ctypes.c_char_p, i32, u64, u64, i32, PSub]
+        L.shockidx_filter_fd.restype = i32
+        L.shockidx_filter_last_stats.argtypes = [vp, ctypes.POINTER(FilterStats)]
+        L.shockidx_filter_last_stats.restype = i32
     PSub_ = ctypes.POINTER(SubsetResult)
     L.shockidx_subset_carry_bytes.argtypes = []
     L.shockidx_subset_carry_bytes.restype = u64

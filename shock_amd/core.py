@@ -645,6 +645,72 @@ class Context:
             d_out.free()
         return r
 
+    # -- the download filters in slabs (shockidx_filter_slab_device and the walk over it) ----------
+    def filter_carry(self) -> "DeviceBuffer":
+        """Device memory for the carry of one filter slab walk (shockidx_filter_carry_bytes; the first
+        slab initialises it)."""
+        return self.alloc(int(self._lib.shockidx_filter_carry_bytes()))
+
+    @staticmethod
+    def filter_carry_state(carry: "DeviceBuffer") -> dict:
+        """The carry's current half: pos (the next Read's section offset), count, bytes, kind, ended."""
+        fc = L.FilterCarry.from_buffer_copy(carry.download(ctypes.sizeof(L.FilterCarry)).tobytes())
+        h = fc.half[fc.cur & 1]
+        return {"pos": int(h.pos), "count": int(h.count), "bytes": int(h.bytes), "kind": int(h.kind),
+                "ended": bool(h.ended)}
+
+    def filter_slab(self, name: str, buf: "DeviceBuffer", base: int, front: int, n: int, end: int, sec_size: int,
+                    carry: "DeviceBuffer", out: "DeviceBuffer", first=None, last=None, out_cap=None) -> SubsetResult:
+        """One slab of a FASTQ section through fq2fa / anonymize: the window is the section bytes
+        [base - front, base + end), n of them owned, where buf holds the section from offset 0 (so base
+        must be a multiple of 16).  Slabs go in order with the carry between them on the device.  OK /
+        EFORMAT: count records and size bytes in out, r.next_pos the carried position; ESPACE: size =
+        the bytes the slab needs; EINVAL: see include/shockidx.h.  Anything but OK or EFORMAT leaves the
+        carry untouched.  first / last default to what the window says."""
+        slab = L.Slab(d_data=buf.ptr + base, n=n, end=end, front=front, base=base,
+                      is_first=int(base - front == 0 if first is None else first),
+                      is_last=int(base + end == sec_size if last is None else last), seq=0, reserved=0)
+        r = L.SubsetResult()
+        pos = ctypes.c_uint64(0)
+        rc = self._lib.shockidx_filter_slab_device(self._h, name.encode(), ctypes.byref(slab), sec_size, carry.ptr,
+                                                   out.ptr, out.nbytes if out_cap is None else out_cap,
+                                                   ctypes.byref(pos), ctypes.byref(r))
+        res = _sub_result(r, rc)
+        res.next_pos = int(pos.value)
+        return res
+
+    def _filter_fd_result(self, r: "L.SubsetResult", rc: int) -> SubsetResult:
+        if rc < 0 and rc not in (L.EINVAL, L.ENOMEM, L.EIO):
+            raise L.ShockIdxError(rc, r.message.decode("utf-8", "replace"))
+        return SubsetResult(count=int(r.count), runs=0, size=int(r.size), status=rc, err=r.message if rc != L.OK else None,
+                            kernel_ms=r.kernel_ms, total_ms=r.total_ms, gather_ms=r.gather_ms)
+
+    def filter_fd_walk(self, name: str, fd: int, off: int, n: int, out_fd: int, slab_bytes: int = 0,
+                       halo_bytes: int = 0) -> SubsetResult:
+        """The section [off, off + n) of fd through fq2fa / anonymize, always slab by slab
+        (shockidx_filter_fd_walk; 0: sized to the device budget), the stream written to out_fd (a file, a
+        pipe, a socket).  status OK, EFORMAT (Go's text, after the delivered bytes were written), ENOMEM
+        (a record no slot can hold), EIO (the write failed) or EINVAL; count / size = what was delivered."""
+        r = L.SubsetResult()
+        rc = self._lib.shockidx_filter_fd_walk(self._h, name.encode(), fd, off, n, out_fd, slab_bytes, halo_bytes,
+                                               ctypes.byref(r))
+        return self._filter_fd_result(r, rc)
+
+    def filter_fd(self, name: str, fd: int, off: int, n: int, out_fd: int) -> SubsetResult:
+        """The same through shockidx_filter_fd: the whole path when the section, its output and the
+        workspace fit the device budget, else the walk (anonymize: FASTQ sections only)."""
+        r = L.SubsetResult()
+        rc = self._lib.shockidx_filter_fd(self._h, name.encode(), fd, off, n, out_fd, ctypes.byref(r))
+        return self._filter_fd_result(r, rc)
+
+    def filter_stats(self) -> dict:
+        """How the last filter_fd / filter_fd_walk ran (shockidx_filter_last_stats)."""
+        st = L.FilterStats()
+        rc = self._lib.shockidx_filter_last_stats(self._h, ctypes.byref(st))
+        if rc != L.OK:
+            raise L.ShockIdxError(rc, "shockidx_filter_last_stats")
+        return {k: int(getattr(st, k)) for k, _ in L.FilterStats._fields_}
+
     # -- the sectioned stream (request/streamer.go:78-98) -----------------------------------------
     def stream_filter_device(self, name, d_data: int, data_len: int, d_secs: int, nsecs: int, d_out: int,
                              out_cap: int) -> SubsetResult:
@@ -778,6 +844,7 @@ class SubsetResult:
     gathered: bytes | None = None
     err_section: int = -1  # stream_filter_device: the failing section (Streamer.ESection)
     err_part: int = -1  # download_plan: the failing part
+    next_pos: int = 0  # filter_slab: the carried position (section offset of the next Read)
 
     @property
     def ok(self) -> bool:

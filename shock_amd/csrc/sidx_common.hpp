@@ -223,6 +223,30 @@ enum ChunkSlabStatus : int { CRS_OK = 0, CRS_BEFORE = 1, CRS_ENDED = 2 };
 using namespace chunk_ctl;
 static_assert(CRS_WORDS == 8, "the host reads the control words through 64 pinned bytes");
 
+// The download filters' slab step (shockidx_filter_slab_device).  The carry: where the filter's
+// reader stands in the section (pos: the start of the next Read, fastq.go:50-132), what it has
+// delivered (records: anonymize's counter, anonymize.go:44-47; bytes), the filter and the format the
+// first slab resolved, and whether the stream has ended (EOF or a reader error).  Two halves as
+// ChunkCarry: a slab reads half `cur` and writes the other, then flips `cur`; a slab that returns
+// anything but OK or EFORMAT writes neither.
+struct FiltCarryHalf {
+  u64 pos, count, bytes, kind, ended, pad[3];
+};
+struct FiltCarry {
+  u64 cur, pad[7];
+  FiltCarryHalf half[2];
+};
+// The slab step's control words.  k_filt_slab_begin writes the first eight (the host's first stop:
+// what the carry held, FS_VEND = where this slab's view [FS_POS, FS_VEND) ends), k_filt_slab_settle
+// the next seven (the second stop); FS_FIRSTBAD is k_fq_spans' first-bad word.
+namespace filt_ctl {
+enum FiltSlabCtl : int { FS_STATUS = 0, FS_POS, FS_VEND, FS_COUNT, FS_BYTES, FS_KIND, FS_R6, FS_R7,
+                         FS_KE, FS_CODE, FS_TOTAL, FS_NEWPOS, FS_ENDED, FS_ERR, FS_R14, FS_FIRSTBAD, FS_WORDS };
+enum FiltSlabStatus : int { FSS_OK = 0, FSS_OUTSIDE = 1, FSS_ENDED = 2, FSS_KIND = 3 };
+constexpr u32 FS_CODE_INTERNAL = 0xFF;  // FS_CODE: the index's terminal record passes Read (never expected)
+}  // namespace filt_ctl
+static_assert(filt_ctl::FS_WORDS == 16, "the host reads the control words through 64 pinned bytes, eight at a time");
+
 // Device result of finalize (mirrored by shockidx_result in include/shockidx.h).
 struct DevResult {
   u64 count;       // records (rows) produced, Go's `count`

@@ -45,8 +45,12 @@ __device__ __forceinline__ u32 ndigits(u64 v) {  // compares, no divisions
 // qual_len), the output length and Read's status for the checks the index did not make.
 // ord (nullable): each record's ordinal within its section, the sectioned stream's anonymize counter
 // (sidx_stream.hip: the reader, and with it the counter, restarts at every section); null: the flat index.
+// BASE: the slab walk's counter (shockidx_filter_slab_device): *cbase + i + 1, *cbase = the records the
+// earlier slabs delivered (a control word on the device: no host stop between the carry and this kernel).
+template <bool BASE>
 __global__ __launch_bounds__(256) void k_fq_spans(const uint8_t *data, u64 n, const u64 *rows, u64 K, int kind,
-                                                  u32 *spans, u64 *outlen, u64 *firstbad, const u32 *ord) {
+                                                  u32 *spans, u64 *outlen, u64 *firstbad, const u32 *ord,
+                                                  const u64 *cbase) {
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= K) return;
   {  // spans already placed from the tile pass (sidx_kernels.hip k_fq_spans_place): drop the mark
@@ -88,7 +92,7 @@ __global__ __launch_bounds__(256) void k_fq_spans(const uint8_t *data, u64 n, co
   sp[2] = (u32)(slo - off); sp[3] = (u32)(shi - slo);
   sp[4] = (u32)(qlo - off); sp[5] = (u32)(qhi - qlo);
   outlen[i] = kind == FILT_FQ2FA ? (ihi - ilo) + (shi - slo) + 3
-                                 : (u64)ndigits(ord ? (u64)ord[i] + 1 : i + 1) + (shi - slo) + (qhi - qlo) + 6;
+                                 : (u64)ndigits(BASE ? *cbase + i + 1 : ord ? (u64)ord[i] + 1 : i + 1) + (shi - slo) + (qhi - qlo) + 6;
 }
 
 // ---- k_fq_write: output-centric (round 3) ----------------------------------------------------
@@ -247,13 +251,18 @@ __device__ __forceinline__ void fw_store(uint8_t *p, const uint4 v) {
   __builtin_nontemporal_store(x, reinterpret_cast<v4u *>(p));
 }
 
-// the filter as a template argument: one code path per kernel; ORD: the anonymize counter of record r
-// is ord[r] + 1 (its ordinal within its section, the sectioned stream) instead of r + 1
-template <int kind, bool ORD>
+// the filter as a template argument: one code path per kernel; CTR: the anonymize counter of record r
+// is r + 1 (CTR_FLAT), ord[r] + 1 (CTR_ORD: its ordinal within its section, the sectioned stream) or
+// *cbase + r + 1 (CTR_BASE: the slab walk, *cbase records delivered by the earlier slabs -- up to 20
+// digits: ndigits, the "more than 8 digits" path of fw_record and fw_byte take any u64)
+enum FwCounter : int { CTR_FLAT = 0, CTR_ORD = 1, CTR_BASE = 2 };
+template <int kind, int CTR>
 __global__ __launch_bounds__(FW_THREADS) void k_fq_write(const uint8_t *data, u64 n, const u64 *rows, const u32 *spans,
                                                          const u64 *outoff, const u64 *wfirst, u64 K, u64 total,
-                                                         uint8_t *out, const u32 *ord) {
-  auto counter = [&](u64 r) -> u64 { return ORD ? (u64)ord[r] + 1 : r + 1; };
+                                                         uint8_t *out, const u32 *ord, const u64 *cbase) {
+  constexpr bool ORD = CTR == CTR_ORD;
+  const u64 cb = CTR == CTR_BASE ? *cbase : 0;
+  auto counter = [&](u64 r) -> u64 { return ORD ? (u64)ord[r] + 1 : cb + r + 1; };
   __shared__ u64 s_out[FW_RECS + 1];
   __shared__ u64 s_off[FW_RECS];
   __shared__ uint4 s_sp[FW_RECS];
@@ -336,6 +345,143 @@ __global__ void k_fq_read_status(const uint8_t *data, u64 n, u64 s, u32 *out) {
   wa.g = data; wa.end = n; wa.eof = 1; wa.lane = threadIdx.x & 63; wa.front = 0;
   const u32 st = fastq_read_status(wa, s);
   if (threadIdx.x == 0) *out = st;
+}
+
+// ---- the slab step's control kernels (shockidx_filter_slab_device) ---------------------------
+// A slab's view is the section bytes [pos, vend): pos the carried start of the next Read, vend the
+// section's end on the last slab and else the byte after the window's last '\n' -- so every line of
+// the view is complete, and the record index and spans of the view (the kernels above, unchanged)
+// are those of the section up to the first Read that is not settled (its blank lines and four
+// lines do not all find their '\n' inside the window): k_filt_slab_settle counts that Read's lines
+// itself, and an error of a settled Read is the stream's own.
+using namespace filt_ctl;
+
+// The carry into the control words and the view's end.  win: the window's first byte (section byte
+// wlo); [wlo, whi) the window; own_end = base + n.  One workgroup: the last '\n' is looked for from
+// the window's end backwards, 4 KiB a step (it is the window's last byte or close to it, unless a
+// line is longer than the halo).
+__global__ __launch_bounds__(256) void k_filt_slab_begin(const uint8_t *win, u64 wlo, u64 whi, u64 own_end, int first,
+                                                         int last, int kind, const FiltCarry *carry, u64 *st) {
+  __shared__ u64 s_hit;
+  __shared__ u64 s_pos;
+  __shared__ u32 s_status;
+  if (threadIdx.x == 0) {
+    FiltCarryHalf h = {};
+    h.kind = (u64)kind;
+    if (!first) h = carry->half[carry->cur & 1];
+    u32 status = FSS_OK;
+    if (h.ended) status = FSS_ENDED;
+    else if (h.kind != (u64)kind) status = FSS_KIND;
+    else if (h.pos < wlo || h.pos > own_end) status = FSS_OUTSIDE;
+    st[FS_STATUS] = status;
+    st[FS_POS] = h.pos;
+    st[FS_COUNT] = h.count;
+    st[FS_BYTES] = h.bytes;
+    st[FS_KIND] = h.kind;
+    st[FS_R6] = st[FS_R7] = 0;
+    s_pos = h.pos;
+    s_status = status;
+    s_hit = 0;
+  }
+  __syncthreads();
+  if (s_status != FSS_OK) {
+    if (threadIdx.x == 0) st[FS_VEND] = s_pos;
+    return;
+  }
+  const u64 pos = s_pos;
+  u64 vend = whi;
+  if (!last) {
+    vend = pos;
+    for (u64 hi = whi; hi > pos;) {
+      const u64 lo = hi - pos > 4096 ? hi - 4096 : pos;
+      const u64 a = lo + 16ull * threadIdx.x;
+      u64 hit = 0;  // the byte after this thread's last '\n'
+      for (u64 p = a; p < a + 16 && p < hi; ++p)
+        if (win[p - wlo] == '\n') hit = p + 1;
+      if (hit) atomicMax((unsigned long long *)&s_hit, (unsigned long long)hit);
+      __syncthreads();
+      const u64 found = s_hit;
+      __syncthreads();  // (every thread has read it before the next step's atomicMax)
+      if (found) { vend = found; break; }
+      hi = lo;
+    }
+  }
+  if (threadIdx.x == 0) st[FS_VEND] = vend;
+}
+
+// One wave, after k_fq_spans and the scan of the output lengths over the view's K index rows (view
+// offsets): the records this slab delivers, Read's status for the stream, the bytes they take and
+// where the reader stands afterwards.  index_err: the record index ended in a format error (its
+// terminal record, at the end of row K - 1, is re-read in Read's order as filter_section does).
+// own: view offsets below it are owned (a Read that starts at or after it is a later slab's; ~0: the
+// last slab owning its whole window, the Read at the section's very end included); last: the view
+// ends the section (everything is settled).
+__global__ __launch_bounds__(64) void k_filt_slab_settle(const uint8_t *view, u64 vn, const u64 *rows, u64 K,
+                                                         int index_err, u64 own, int last, const u64 *outlen,
+                                                         const u64 *outoff, u64 sec_size, u64 *st) {
+  auto start_of = [&](u64 i) -> u64 { return i < K ? rows[2 * i] : K ? rows[2 * (K - 1)] + rows[2 * (K - 1) + 1] : 0; };
+  const u64 fb = st[FS_FIRSTBAD];
+  u64 kc = K;
+  u32 code = ST_END;
+  WaveAcc wa;
+  wa.g = view; wa.end = vn; wa.eof = 1; wa.lane = threadIdx.x & 63; wa.front = 0;
+  // Not the section's end: the Read after the K rows is settled only when its blank lines and four
+  // lines all lie in the view.  (Read tolerates EOF on the quality line, fastq.go:119-122: over a
+  // view cut after the plus line it would report a length mismatch that the next bytes may undo.)
+  bool open_tail = false;
+  if (!last && fb == ~0ull) {
+    u64 y = 0, e = 0;
+    open_tail = wa.find(C_NOTNL, start_of(K), NOLIM, y) != FR_FOUND;
+    for (int k = 0; k < 4 && !open_tail; ++k) {
+      open_tail = wa.find(C_NL, y, NOLIM, e) != FR_FOUND;
+      y = e + 1;
+    }
+  }
+  if (fb != ~0ull) {  // a record the index accepted and Read rejects (blank-looking ID or sequence)
+    kc = fb >> 4;
+    code = (u32)(fb & 15);
+  } else if (open_tail) {
+    code = ST_END;
+  } else if (index_err) {
+    code = fastq_read_status(wa, start_of(K));
+    if (code == ST_OK || code == ST_END) code = FS_CODE_INTERNAL;
+  } else if (K && start_of(K) == vn && view[vn - 1] != '\n') {
+    kc = K - 1;  // the quality line ends at EOF: Read returns the record with io.EOF, dropped (the last slab only)
+  }
+  if (threadIdx.x != 0) return;
+  u64 ke = kc;
+  if (own != ~0ull) {  // the owned rows: the first row that starts at or after own
+    u64 lo = 0, hi = kc;
+    while (lo < hi) {
+      const u64 mid = (lo + hi) / 2;
+      if (rows[2 * mid] < own) lo = mid + 1; else hi = mid;
+    }
+    ke = lo;
+  }
+  // the Read after the kc records (the one that fails, or on the last slab returns io.EOF) is owned too
+  const bool final_owned = ke == kc && (own == ~0ull || start_of(kc) < own);
+  const bool err = code != ST_END && final_owned;
+  const bool ended = err || (last && final_owned);
+  st[FS_KE] = ke;
+  st[FS_CODE] = err ? code : ST_END;
+  st[FS_ERR] = err;
+  st[FS_TOTAL] = ke ? outoff[ke - 1] + outlen[ke - 1] : 0;
+  st[FS_ENDED] = ended ? 1 : 0;
+  st[FS_NEWPOS] = ended && !err ? sec_size : st[FS_POS] + start_of(ke);
+  st[FS_R14] = 0;
+}
+
+// the end state into the carry's other half (the first slab: half 0), after the records were written
+__global__ void k_filt_slab_commit(FiltCarry *carry, const u64 *st, int first) {
+  const u64 nh = first ? 0 : (carry->cur & 1) ^ 1;
+  FiltCarryHalf h = {};
+  h.pos = st[FS_NEWPOS];
+  h.count = st[FS_COUNT] + st[FS_KE];
+  h.bytes = st[FS_BYTES] + st[FS_TOTAL];
+  h.kind = st[FS_KIND];
+  h.ended = st[FS_ENDED];
+  carry->half[nh] = h;
+  carry->cur = nh;
 }
 
 // ---- anonymize over a FASTA section (fasta.go:40-88 Read, :216-218 Format) -----------------
@@ -799,25 +945,61 @@ using namespace sidx;
 
 extern "C" hipError_t sidx_filter_spans(const uint8_t *data, u64 n, const u64 *rows, u64 K, int kind, u32 *spans,
                                         u64 *outlen, u64 *firstbad, const u32 *ord, hipStream_t s) {
-  if (K) hipLaunchKernelGGL(k_fq_spans, dim3((u32)((K + 255) / 256)), dim3(256), 0, s, data, n, rows, K, kind, spans,
-                            outlen, firstbad, ord);
+  if (K) hipLaunchKernelGGL(k_fq_spans<false>, dim3((u32)((K + 255) / 256)), dim3(256), 0, s, data, n, rows, K, kind, spans,
+                            outlen, firstbad, ord, (const u64 *)nullptr);
+  return hipGetLastError();
+}
+// the slab walk's spans: the counter of record i is *cbase + i + 1
+extern "C" hipError_t sidx_filter_spans_base(const uint8_t *data, u64 n, const u64 *rows, u64 K, int kind, u32 *spans,
+                                             u64 *outlen, u64 *firstbad, const u64 *cbase, hipStream_t s) {
+  if (K) hipLaunchKernelGGL(k_fq_spans<true>, dim3((u32)((K + 255) / 256)), dim3(256), 0, s, data, n, rows, K, kind, spans,
+                            outlen, firstbad, (const u32 *)nullptr, cbase);
   return hipGetLastError();
 }
 
 // wfirst: total / FW_BLOCK + 1 words (the first record of every output block)
-extern "C" hipError_t sidx_filter_write(const uint8_t *data, u64 n, const u64 *rows, const u32 *spans, const u64 *outlen,
-                                        const u64 *outoff, u64 K, u64 total, int kind, u64 *wfirst, uint8_t *out,
-                                        const u32 *ord, hipStream_t s) {
+static hipError_t filter_write(const uint8_t *data, u64 n, const u64 *rows, const u32 *spans, const u64 *outlen,
+                                const u64 *outoff, u64 K, u64 total, int kind, u64 *wfirst, uint8_t *out, const u32 *ord,
+                                const u64 *cbase, hipStream_t s) {
   if (!K || !total) return hipSuccess;
   const u64 nblocks = (total + FW_BLOCK - 1) / FW_BLOCK;
   hipLaunchKernelGGL(k_fw_plan, dim3((u32)((K + 255) / 256)), dim3(256), 0, s, outoff, outlen, K, nblocks, wfirst);
-#define SIDX_FW_LAUNCH(KIND, ORD)                                                                                  \
-  hipLaunchKernelGGL((k_fq_write<KIND, ORD>), dim3((u32)nblocks), dim3(FW_THREADS), 0, s, data, n, rows, spans, outoff, \
-                     wfirst, K, total, out, ord)
-  if (kind == FILT_FQ2FA) SIDX_FW_LAUNCH(FILT_FQ2FA, false);  // fq2fa writes no counter
-  else if (ord) SIDX_FW_LAUNCH(FILT_ANON_FQ, true);
-  else SIDX_FW_LAUNCH(FILT_ANON_FQ, false);
+#define SIDX_FW_LAUNCH(KIND, CTR)                                                                                  \
+  hipLaunchKernelGGL((k_fq_write<KIND, CTR>), dim3((u32)nblocks), dim3(FW_THREADS), 0, s, data, n, rows, spans, outoff, \
+                     wfirst, K, total, out, ord, cbase)
+  if (kind == FILT_FQ2FA) SIDX_FW_LAUNCH(FILT_FQ2FA, CTR_FLAT);  // fq2fa writes no counter
+  else if (ord) SIDX_FW_LAUNCH(FILT_ANON_FQ, CTR_ORD);
+  else if (cbase) SIDX_FW_LAUNCH(FILT_ANON_FQ, CTR_BASE);
+  else SIDX_FW_LAUNCH(FILT_ANON_FQ, CTR_FLAT);
 #undef SIDX_FW_LAUNCH
+  return hipGetLastError();
+}
+extern "C" hipError_t sidx_filter_write(const uint8_t *data, u64 n, const u64 *rows, const u32 *spans, const u64 *outlen,
+                                        const u64 *outoff, u64 K, u64 total, int kind, u64 *wfirst, uint8_t *out,
+                                        const u32 *ord, hipStream_t s) {
+  return filter_write(data, n, rows, spans, outlen, outoff, K, total, kind, wfirst, out, ord, nullptr, s);
+}
+// the slab walk's writer: the counter of record r is *cbase + r + 1
+extern "C" hipError_t sidx_filter_write_base(const uint8_t *data, u64 n, const u64 *rows, const u32 *spans,
+                                             const u64 *outlen, const u64 *outoff, u64 K, u64 total, int kind, u64 *wfirst,
+                                             uint8_t *out, const u64 *cbase, hipStream_t s) {
+  return filter_write(data, n, rows, spans, outlen, outoff, K, total, kind, wfirst, out, nullptr, cbase, s);
+}
+// the slab step (st: FS_WORDS control words on the device)
+extern "C" hipError_t sidx_filt_slab_begin(const uint8_t *win, u64 wlo, u64 whi, u64 own_end, int first, int last, int kind,
+                                           const FiltCarry *carry, u64 *st, hipStream_t s) {
+  hipLaunchKernelGGL(k_filt_slab_begin, dim3(1), dim3(256), 0, s, win, wlo, whi, own_end, first, last, kind, carry, st);
+  return hipGetLastError();
+}
+extern "C" hipError_t sidx_filt_slab_settle(const uint8_t *view, u64 vn, const u64 *rows, u64 K, int index_err, u64 own,
+                                            int last, const u64 *outlen, const u64 *outoff, u64 sec_size, u64 *st,
+                                            hipStream_t s) {
+  hipLaunchKernelGGL(k_filt_slab_settle, dim3(1), dim3(64), 0, s, view, vn, rows, K, index_err, own, last, outlen, outoff,
+                     sec_size, st);
+  return hipGetLastError();
+}
+extern "C" hipError_t sidx_filt_slab_commit(FiltCarry *carry, const u64 *st, int first, hipStream_t s) {
+  hipLaunchKernelGGL(k_filt_slab_commit, dim3(1), dim3(1), 0, s, carry, st, first);
   return hipGetLastError();
 }
 extern "C" u64 sidx_filter_block() { return FW_BLOCK; }

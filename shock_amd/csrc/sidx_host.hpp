@@ -23,6 +23,7 @@
 
 namespace sidx {
 struct ChunkWalkDev;  // sidx_chunkwalk.hpp
+struct FiltWalkDev;   // sidx_filtwalk.hpp
 }
 
 namespace sidx_host {
@@ -138,6 +139,9 @@ struct shockidx_ctx {
   Buf<uint8_t> d_spar{bufs};       // subset walk: the parent window (bytes)
   Buf<uint8_t> d_sruns{bufs};      //   the carry, then one slab's runs (bytes)
   shockidx_subset_stats subset_stats = {};  //   how the last file-level subset build ran (shockidx_subset_last_stats)
+  Buf<uint8_t> d_fview{bufs};      // filter slab call: the window from the carried position on, 16-byte aligned (bytes)
+  Buf<uint8_t> d_fout{bufs};       // filter walk / whole path: the carry, then one slab's (the section's) output (bytes)
+  shockidx_filter_stats filter_stats = {};  //   how the last file-level filter call ran (shockidx_filter_last_stats)
   hipStream_t s_copy = nullptr;    // slab-pipelined host builds: the H2D stream
   uint8_t *h_rows[2] = {nullptr, nullptr};  // slab-pipelined fd builds: pinned row staging (D2H)
   // download filters over FASTQ: the tile pass keeps each record's line ends (k_fq_tiles<true>)
@@ -262,6 +266,24 @@ int filter_kind(const char *filter);
 // ignored, the section's own status with the count / size a write would deliver
 int filter_section(shockidx_ctx *c, int kind, const uint8_t *dd, sidx::u64 n, void *d_out, sidx::u64 out_cap,
                    shockidx_subset_result *res, bool size_only);
+
+// ---- the download filters in slabs (sidx_filter_api.cpp, sidx_walks.cpp) -----------------------
+// the device-side figures the walk's sizing takes (sidx_filtwalk.hpp) for views of len bytes
+sidx::FiltWalkDev filter_walk_dev(shockidx_ctx *c, sidx::u64 len);
+// One slab over the window [wlo, whi) of the section at win, bytes below own_end owned, the carry on
+// the device.  Returns like shockidx_filter_slab_device (the format is FASTQ: detection is the
+// caller's); waits for the stream.
+int filter_slab_run(shockidx_ctx *c, int kind, const uint8_t *win, sidx::u64 wlo, sidx::u64 whi, sidx::u64 own_end,
+                    bool first, bool last, sidx::u64 sec_size, sidx::FiltCarry *carry, uint8_t *d_out, sidx::u64 out_cap,
+                    sidx::u64 *next_pos, shockidx_subset_result *res);
+// shockidx_filter_fd: detection (anonymize), then the whole path or the walk
+int filter_fd_any(shockidx_ctx *c, int kind, const char *filter, int fd, sidx::u64 off, sidx::u64 n, int out_fd,
+                  shockidx_subset_result *res);
+// The slab walk over the section [off, off + n) of fd (kind: filter_kind; S-byte slabs, 0: sized
+// from the device budget; halo 0: the default), each slab's output to out_fd.  c->filter_stats says
+// how it ran.
+int filter_fd_walk(shockidx_ctx *c, int kind, const char *filter, int fd, sidx::u64 off, sidx::u64 n, int out_fd,
+                   sidx::u64 S, sidx::u64 halo, shockidx_subset_result *res);
 
 // ---- staging and copy-out (sidx_build.cpp) ---------------------------------------------------
 // a row table the caller frees with free() / shockidx_free (2 MiB aligned when large)

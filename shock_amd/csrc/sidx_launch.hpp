@@ -129,6 +129,19 @@ hipError_t sidx_filter_spans(const uint8_t *data, sidx::u64 n, const sidx::u64 *
 hipError_t sidx_filter_write(const uint8_t *data, sidx::u64 n, const sidx::u64 *rows, const sidx::u32 *spans,
     const sidx::u64 *outlen, const sidx::u64 *outoff, sidx::u64 K, sidx::u64 total, int kind, sidx::u64 *wfirst,
     uint8_t *out, const sidx::u32 *ord, hipStream_t s);
+// the filters' slab step (sidx_filter.hip): spans and writer with the counter *cbase + r + 1, and the
+// control kernels around them (st: the FS_* control words, sidx_common.hpp)
+hipError_t sidx_filter_spans_base(const uint8_t *data, sidx::u64 n, const sidx::u64 *rows, sidx::u64 K, int kind,
+    sidx::u32 *spans, sidx::u64 *outlen, sidx::u64 *firstbad, const sidx::u64 *cbase, hipStream_t s);
+hipError_t sidx_filter_write_base(const uint8_t *data, sidx::u64 n, const sidx::u64 *rows, const sidx::u32 *spans,
+    const sidx::u64 *outlen, const sidx::u64 *outoff, sidx::u64 K, sidx::u64 total, int kind, sidx::u64 *wfirst,
+    uint8_t *out, const sidx::u64 *cbase, hipStream_t s);
+hipError_t sidx_filt_slab_begin(const uint8_t *win, sidx::u64 wlo, sidx::u64 whi, sidx::u64 own_end, int first, int last,
+    int kind, const sidx::FiltCarry *carry, sidx::u64 *st, hipStream_t s);
+hipError_t sidx_filt_slab_settle(const uint8_t *view, sidx::u64 vn, const sidx::u64 *rows, sidx::u64 K, int index_err,
+    sidx::u64 own, int last, const sidx::u64 *outlen, const sidx::u64 *outoff, sidx::u64 sec_size, sidx::u64 *st,
+    hipStream_t s);
+hipError_t sidx_filt_slab_commit(sidx::FiltCarry *carry, const sidx::u64 *st, int first, hipStream_t s);
 sidx::u64 sidx_filter_block();
 sidx::u32 sidx_filter_recs();
 hipError_t sidx_filter_read_status(const uint8_t *data, sidx::u64 n, sidx::u64 start, sidx::u32 *out,

@@ -153,8 +153,10 @@ struct TwoSlots {
   Err res;
   SlabEvents events;
   PageCacheSource src;
-  TwoSlots(shockidx_ctx *ctx, int fd, sidx::u64 n, Err r) : c(ctx), res(r), events(2, ctx->s_copy), src(ctx, fd, 0, n, r) {}
-  // file bytes [lo, hi) to offset d of slot i, their arrival recorded in the slot's event (an
+  // (the n bytes from file offset `off` on: a whole file, or the section a filtered download reads)
+  TwoSlots(shockidx_ctx *ctx, int fd, sidx::u64 off, sidx::u64 n, Err r)
+      : c(ctx), res(r), events(2, ctx->s_copy), src(ctx, fd, off, n, r) {}
+  // section bytes [lo, hi) to offset d of slot i, their arrival recorded in the slot's event (an
   // empty range copies nothing and still records it)
   int stage(int i, sidx::u64 d, sidx::u64 lo, sidx::u64 hi) {
     if (int rc = src.copy_range(c->d_slot[i] + d, lo, hi, lo)) return rc;
@@ -194,6 +196,14 @@ int drain_rows(shockidx_ctx *c, const sidx::u64 *d_tab, sidx::u64 m, sidx::u64 f
 // read_prefix + strerror, a file that ends early short_msg, a failed copy names copy_what.
 int file_to_device(shockidx_ctx *c, int fd, sidx::u64 off, sidx::u64 total, uint8_t *dst, const char *read_prefix,
                    const char *short_msg, const char *copy_what, Err res);
+
+// total bytes of device memory at d_src to the descriptor out_fd, in order: through the pinned
+// buffer c->h_rows[0], 64 MiB at a time, each piece waited for on c->stream and then written with
+// write(2) -- out_fd may be a pipe or a socket (no lseek, no pwrite); short writes and EINTR are
+// handled, and a reader that has gone away is EPIPE here, not a signal.  A failed write is
+// SHOCKIDX_EIO with the errno text.  *t_d2h / *t_write grow by the time the copies / writes took.
+int drain_bytes(shockidx_ctx *c, const uint8_t *d_src, sidx::u64 total, int out_fd, double *t_d2h, double *t_write,
+                Err res);
 
 // count, format, path and the times of a walk that ends here (t0: when it began); what is neither
 // row copy nor kernel is waiting for the PCIe stream

@@ -1,11 +1,15 @@
 // sidx_walks.cpp -- the carried-state walks over a node's file: the column index, the subset
-// indexes and the chunkrecord index slab by slab through two device slots, each loop's state in a
-// device carry, rows to the sink as they are made.  sidx_colwalk.hpp, sidx_subwalk.hpp and
-// sidx_chunkwalk.hpp hold their arithmetic and decisions; the pieces they share with the record
+// indexes, the chunkrecord index and the download filters slab by slab through two device slots,
+// each loop's state in a device carry, rows to the sink (the filters: bytes to a descriptor) as they
+// are made.  sidx_colwalk.hpp, sidx_subwalk.hpp, sidx_chunkwalk.hpp and sidx_filtwalk.hpp hold their
+// arithmetic and decisions; the pieces they share with the record
 // pipelines (sidx_pipeline.cpp) are declared in sidx_walk.hpp and defined here.
 #include <errno.h>
 #include <hip/hip_runtime.h>
+#include <pthread.h>
+#include <signal.h>
 #include <string.h>
+#include <time.h>
 #include <unistd.h>
 
 #include <string>
@@ -14,6 +18,7 @@
 #include "sidx_common.hpp"
 #include "sidx_colwalk.hpp"
 #include "sidx_chunkwalk.hpp"
+#include "sidx_filtwalk.hpp"
 #include "sidx_subwalk.hpp"
 #include "sidx_launch.hpp"
 #include "sidx_walk.hpp"
@@ -130,7 +135,7 @@ int column_fd_walk(shockidx_ctx *c, int fd, u64 n, u32 column, u64 S, u64 halo, 
     return rc;
   ColCarry *carry = c->d_colb.as<ColCarry>();
   void *ws = c->d_colb + carry_b;
-  TwoSlots w(c, fd, n, res);
+  TwoSlots w(c, fd, 0, n, res);
   HIPCHK(w.events.create(), "event");
   ColRowCursor cur;
   u64 next = 0;
@@ -239,7 +244,7 @@ int subset_fd_walk(shockidx_ctx *c, int ids_fd, u64 n, int parent_fd, u64 parent
   SubCarry *carry = c->d_sruns.as<SubCarry>();
   u64 *d_runs = (u64 *)(c->d_sruns + carry_b);
   HIPCHK(hipMemsetAsync(carry, 0, carry_b, s), "carry");
-  TwoSlots w(c, ids_fd, n, res);
+  TwoSlots w(c, ids_fd, 0, n, res);
   HIPCHK(w.events.create(), "event");
   SubCursor cur;
   SubWindow win = subwalk_window_at(0, W, parent_count);
@@ -344,7 +349,7 @@ int chunk_fd_walk(shockidx_ctx *c, int fd, u64 n, int fmt, u64 chunk, u64 S, Row
                                    {&c->d_crc, dv.carry_bytes}, {&c->d_rows, row_cap}}, res))
     return rc;
   ChunkCarry *carry = c->d_crc.as<ChunkCarry>();
-  TwoSlots w(c, fd, n, res);
+  TwoSlots w(c, fd, 0, n, res);
   HIPCHK(w.events.create(), "event");
   auto stage = [&](u64 k) {  // slab k's slot bytes (empty for an empty file) into slot k mod 2
     const ChunkSlot p = chunkwalk_slot(k, S, n);
@@ -388,6 +393,211 @@ int chunk_fd_walk(shockidx_ctx *c, int fd, u64 n, int fmt, u64 chunk, u64 S, Row
   finish_walk(res, kfmt, cur.total, 6, res->kernel_ms, res->kernel_ms, t_d2h, t0);
   res->status = SHOCKIDX_OK;
   return SHOCKIDX_OK;
+}
+
+// ---- the download filters' walk ----------------------------------------------------------------
+// GET /node/{id}?download&filter=F (controller/node/single.go:490-526; its seek / length form
+// :194-257) over a FASTQ section of a file: the section slab by slab through the two slots (slab
+// k + 1 copied on the copy stream while slab k runs), the reader's position and the filter's counter
+// in the device carry, each slab's output through the pinned buffer to out_fd in order -- what
+// io.Copy writes to the response (request/streamer.go:91-96), the bytes before a reader error
+// included.  sidx_filtwalk.hpp holds the sizing and the restart rule.  The device holds the two
+// slots, the view, the carry with one slab's output, one slab's workspace (c->d_sub, the tile block
+// of the view's record index) and one slab's rows, all sized up front.
+namespace {
+
+// every byte of [p, p + k) to fd.  SIGPIPE is blocked around the writes, and one raised by them is
+// taken off the thread, so a reader that closed its end is EPIPE in the result whatever the
+// process does with the signal.
+int write_all(int fd, const uint8_t *p, size_t k, Err res) {
+  sigset_t pipe_set, old, pend;
+  sigemptyset(&pipe_set);
+  sigaddset(&pipe_set, SIGPIPE);
+  (void)pthread_sigmask(SIG_BLOCK, &pipe_set, &old);
+  (void)sigpending(&pend);
+  const bool was_pending = sigismember(&pend, SIGPIPE) == 1;
+  int err = 0;
+  while (k) {
+    const ssize_t r = write(fd, p, k);
+    if (r < 0 && errno == EINTR) continue;
+    if (r <= 0) {
+      err = r < 0 ? errno : EIO;
+      break;
+    }
+    p += r;
+    k -= (size_t)r;
+  }
+  if (err == EPIPE && !was_pending) {
+    const struct timespec zero = {0, 0};
+    while (sigtimedwait(&pipe_set, nullptr, &zero) < 0 && errno == EINTR) {}
+  }
+  (void)pthread_sigmask(SIG_SETMASK, &old, nullptr);
+  return err ? set_msg(res, SHOCKIDX_EIO, std::string("write: ") + strerror(err)) : 0;
+}
+
+void filter_stats_end(shockidx_ctx *c, shockidx_subset_result *res, double t_d2h, double t_write, double t0) {
+  shockidx_filter_stats &st = c->filter_stats;
+  st.peak_bytes = workspace_bytes(c);
+  st.kernel_us = (u64)(res->kernel_ms * 1000.0);
+  st.d2h_us = (u64)(t_d2h * 1000.0);
+  st.write_us = (u64)(t_write * 1000.0);
+  res->gather_ms = t_d2h + t_write;
+  res->total_ms = now_ms() - t0;
+}
+
+// The whole path: the section resident, filter_section over it, the output written.
+int filter_fd_whole(shockidx_ctx *c, int kind, int fd, u64 off, u64 n, int out_fd, bool fastq, shockidx_subset_result *res) {
+  const double t0 = now_ms();
+  c->filter_stats.path = 1;
+  double t_d2h = 0, t_write = 0;
+  auto run = [&]() -> int {
+    if (int rc = walk_prereqs(c, res)) return rc;
+    shockidx_result r0;
+    reset_result(&r0);
+    if (int rc = stage_fd(c, fd, off, n, c->stream, &r0)) return forward_error(res, r0, rc);
+    // FASTQ: the worst case (no retry); FASTA / SAM: twice the section first, the exact size on ESPACE
+    u64 cap = fastq ? filtwalk_out_bound(n, filtwalk_rows_cap(n), filtwalk_rows_cap(n)) : 2 * n;
+    int rc = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      if ((rc = c->d_fout.ensure(cap + FILTWALK_PAD, res))) return rc;
+      reset_result(res);
+      rc = filter_section(c, kind, c->d_in, n, c->d_fout, cap, res, false);
+      if (rc != SHOCKIDX_ESPACE) break;
+      cap = res->size;
+    }
+    if (rc != SHOCKIDX_OK && rc != SHOCKIDX_EFORMAT) return rc;
+    // (a failed drain replaces the reader's error: the stream did not reach the caller)
+    if (int rc2 = drain_bytes(c, c->d_fout, res->size, out_fd, &t_d2h, &t_write, res)) return rc2;
+    return rc;
+  };
+  const int rc = run();
+  filter_stats_end(c, res, t_d2h, t_write, t0);
+  return rc;
+}
+
+}  // namespace
+
+int drain_bytes(shockidx_ctx *c, const uint8_t *d_src, u64 total, int out_fd, double *t_d2h, double *t_write, Err res) {
+  for (u64 done = 0; done < total;) {
+    const u64 k = total - done < STAGE_BYTES ? total - done : STAGE_BYTES;
+    const double ta = now_ms();
+    HIPCHK(hipMemcpyAsync(c->h_rows[0], d_src + done, k, hipMemcpyDeviceToHost, c->stream), "output copy");
+    HIPCHK(hipStreamSynchronize(c->stream), "output copy");
+    const double tb = now_ms();
+    if (int rc = write_all(out_fd, c->h_rows[0], k, res)) return rc;
+    if (t_d2h) *t_d2h += tb - ta;
+    if (t_write) *t_write += now_ms() - tb;
+    done += k;
+  }
+  return 0;
+}
+
+int filter_fd_walk(shockidx_ctx *c, int kind, const char *filter, int fd, u64 off, u64 n, int out_fd, u64 S, u64 halo,
+                   shockidx_subset_result *res) {
+  const double t0 = now_ms();
+  shockidx_filter_stats &st = c->filter_stats;
+  memset(&st, 0, sizeof st);
+  st.path = 2;
+  (void)kind;
+  const u64 budget = dev_budget(c);
+  if (!halo) halo = filtwalk_default_halo(budget);
+  const u64 top = n < FILTWALK_MAX_SLAB ? n : FILTWALK_MAX_SLAB;
+  const FiltWalkDev dv = filter_walk_dev(c, top + halo);
+  if (!S) {
+    S = filtwalk_slab_bytes(budget, halo, n, dv);
+    if (!S) return set_msg(res, SHOCKIDX_ENOMEM, "device memory: the filter walk needs at least 32 MiB of its budget");
+  }
+  if (S > n) S = n > FILTWALK_DETECT ? n : FILTWALK_DETECT;
+  if (halo > S) halo = S;  // (the position a slab carries out lies within the next slab's owned bytes)
+  st.slab_bytes = S;
+  st.halo_bytes = halo;
+  double t_d2h = 0, t_write = 0;
+  auto run = [&]() -> int {
+    if (int rc = walk_prereqs(c, res)) return rc;
+    const FiltWalkPlan plan = filtwalk_plan(S, halo, n, dv);
+    if (int rc = exact_workspace(c, {{&c->d_slot[0], plan.slot}, {&c->d_slot[1], plan.slot}, {&c->d_fview, plan.view},
+                                     {&c->d_rows, plan.rows}, {&c->d_sub, plan.ws}, {&c->d_fout, dv.carry_bytes + plan.out}}, res))
+      return rc;
+    FiltCarry *carry = c->d_fout.as<FiltCarry>();
+    uint8_t *d_out = c->d_fout + dv.carry_bytes;
+    TwoSlots w(c, fd, off, n, res);
+    HIPCHK(w.events.create(), "event");
+    auto stage = [&](int i, const FiltSlabPos &p) { return w.stage(i, 0, p.lo, p.lo + p.end); };
+    int i = 0;
+    FiltSlabPos p = filtwalk_slab_at(0, S, halo, n, true);
+    int rc = stage(0, p);
+    while (!rc) {
+      FiltSlabPos q = p;
+      if (!p.last) {  // the slab expected next, on its way while this one runs
+        q = filtwalk_slab_at(p.lo + p.n, S, halo, n, false);
+        if ((rc = stage(i ^ 1, q))) break;
+      }
+      if ((rc = w.wait(i))) break;
+      st.slabs++;
+      shockidx_slab sl;
+      memset(&sl, 0, sizeof sl);
+      sl.d_data = c->d_slot[i].get();
+      sl.n = p.n; sl.end = p.end; sl.front = 0; sl.base = p.lo;
+      sl.is_first = p.first; sl.is_last = p.last;
+      shockidx_subset_result r2;
+      uint64_t pos = 0;
+      rc = shockidx_filter_slab_device(c, filter, &sl, n, carry, d_out, plan.out, &pos, &r2);
+      res->kernel_ms += r2.kernel_ms;
+      if (rc != SHOCKIDX_OK && rc != SHOCKIDX_EFORMAT) {
+        if (rc == SHOCKIDX_ESPACE) rc = set_msg(res, SHOCKIDX_EINTERNAL, "internal error: a slab's output exceeds its bound");
+        else forward_error(res, r2, rc);
+        break;
+      }
+      const int rc_call = rc;
+      if ((rc = drain_bytes(c, d_out, r2.size, out_fd, &t_d2h, &t_write, res))) break;
+      res->count += r2.count;
+      res->size += r2.size;
+      if (rc_call == SHOCKIDX_EFORMAT) { rc = forward_error(res, r2, SHOCKIDX_EFORMAT); break; }
+      if (p.last) break;
+      const FiltNext next = filtwalk_next(p.lo, q.lo, pos);
+      if (next == FiltNext::NoMem) {
+        rc = set_msg(res, SHOCKIDX_ENOMEM, "device memory: a record is longer than a slab slot can hold");
+        break;
+      }
+      if (next == FiltNext::Restart) {  // a fresh slot from the open record on
+        q = filtwalk_slab_at(pos, S, halo, n, false);
+        st.restarts++;
+        if ((rc = stage(i ^ 1, q))) break;
+      }
+      p = q;
+      i ^= 1;
+    }
+    return w.finish(rc);
+  };
+  const int rc = run();
+  filter_stats_end(c, res, t_d2h, t_write, t0);
+  return rc;
+}
+
+int filter_fd_any(shockidx_ctx *c, int kind, const char *filter, int fd, u64 off, u64 n, int out_fd,
+                  shockidx_subset_result *res) {
+  memset(&c->filter_stats, 0, sizeof c->filter_stats);
+  c->filter_stats.path = 1;
+  int kfmt = SHOCKIDX_FMT_FASTQ;  // fq2fa reads everything as FASTQ
+  if (kind == 2) {  // anonymize: DetermineFormat over the section's first 32 KiB (multi.go:43-62)
+    if (!n) return set_msg(res, SHOCKIDX_EFORMAT, "Invalid file type for filter");  // errors.go:20
+    const u64 m = n < FILTWALK_DETECT ? n : FILTWALK_DETECT;
+    shockidx_result r0;
+    reset_result(&r0);
+    if (int rc = stage_fd(c, fd, off, m, c->stream, &r0)) return forward_error(res, r0, rc);
+    if (int rc = resolve_format(c, c->d_in, m, SHOCKIDX_RECORD, SHOCKIDX_FMT_AUTO, c->stream, &kfmt, res)) return rc;
+  }
+  if (!n) return SHOCKIDX_OK;  // fq2fa over an empty section delivers nothing
+  const u64 budget = dev_budget(c);
+  const FiltWalkDev dv = filter_walk_dev(c, n);
+  if (kfmt == SHOCKIDX_FMT_FASTQ) {
+    if (filtwalk_whole_bytes(n, dv) <= budget) return filter_fd_whole(c, kind, fd, off, n, out_fd, true, res);
+    return filter_fd_walk(c, kind, filter, fd, off, n, out_fd, 0, 0, res);
+  }
+  if (filtwalk_whole_other_bytes(n, dv) <= budget) return filter_fd_whole(c, kind, fd, off, n, out_fd, false, res);
+  return set_msg(res, SHOCKIDX_ENOMEM,
+                 kfmt == SHOCKIDX_FMT_FASTA ? "device memory: the FASTA section does not fit the budget (only FASTQ sections are filtered in slabs)"
+                                            : "device memory: the SAM section does not fit the budget (only FASTQ sections are filtered in slabs)");
 }
 
 }  // namespace sidx_host

@@ -60,6 +60,30 @@ def _section_bytes(section) -> bytes:
         return f.read()
 
 
+def Stream(name: str, f, w, seek: int = 0, length: int | None = None) -> int:  # noqa: N802
+    """The Streamer's single-section case over an open file (request/streamer.go:78-98 with
+    R = []SectionReader{io.NewSectionReader(f, seek, length)}, controller/node/single.go:194-257,
+    490-526): the section of the binary file f through filter `name` to the binary file, pipe or
+    socket w, slab by slab when it does not fit the device (shockidx_filter_fd).  Returns the bytes
+    written; raises ShockIndexError with Go's text after the delivered bytes are written (what
+    io.Copy returns after writing them), KeyError for an unknown filter."""
+    if not Has(name):
+        raise KeyError(name)
+    import os
+    fd = f.fileno()
+    size = os.fstat(fd).st_size
+    seek = max(0, min(int(seek), size))
+    n = size - seek if length is None else max(0, min(int(length), size - seek))
+    if hasattr(w, "flush"):
+        w.flush()
+    r = context().filter_fd(name, fd, seek, n, w.fileno())
+    if r.status == L.EFORMAT:
+        raise ShockIndexError(r.err)
+    if r.status != L.OK:
+        raise RuntimeError(f"shockidx_filter_fd: {r.status} {r.err!r}")
+    return r.size
+
+
 def NewReader(f: str, section) -> FilterReader:  # noqa: N802  (filter.go:31-33)
     if not Has(f):
         raise KeyError(f)
